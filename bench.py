@@ -8,16 +8,21 @@ extracts its own 8,000,000-epoch shard, so N = 8 is configs[2]'s 64M epochs (wea
 epochs are independent, no data-path collective).  The feature gather to rank 0 is timed after
 the extraction steps and reported beside `value` (`gather`, `extract_plus_gather`).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--numerics exact|fma]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--numerics exact|fma] [--full]
+                  [--dump-outputs DIR]
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  Extra legs:
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  A plain run sets up, warms up, times
+the K steps and prints the line; --full adds the legs that take runs of their own (cpu_baseline,
+alt_numerics, whole_path.energy, the guard on the reference's recordings, the unit-rows check),
+which are null without it.  --dump-outputs DIR writes the feature rows of the last timed step to
+DIR/features.npy.  Legs:
   roofline      the dominant kernel (window_kernel): its algorithmic bytes per launch / its
                 average launch duration, measured with HIP events that the context records on
                 the stream the kernel runs on, against 8.0 TB/s (MI355X_MICROARCH.md); traffic =
                 HBM bytes per launch from the committed rocprofv3 PMC summary (else null);
-  cpu_baseline  the C restatement (oracle/, reference-faithful full pyramid) timed on the host
-                cores on a bounded sample of the same workload (rank 0's shard; at N > 1 after
-                the gather legs).
+  cpu_baseline  (--full) the C restatement (oracle/, reference-faithful full pyramid) timed on
+                the host cores on a bounded sample of the same workload (rank 0's shard; at
+                N > 1 after the gather legs).
 """
 import argparse
 import json
@@ -82,6 +87,15 @@ def parse():
                          "(latency, per calling thread); logreg: the downstream classifier "
                          "(MLlib LogisticRegressionWithSGD, 100 full-batch iterations) on the 1M "
                          "48-dim feature rows of c3; svm: the same with SVMWithSGD")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the CPU baseline, the other "
+                         "numerics mode (--alt-steps), the live energy bound, the guard on the "
+                         "reference's recordings and the unit-rows check.  Without it a run sets "
+                         "up, warms up, times the steps and prints the line; those fields are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="c3/c32: after the timed steps, write what the last timed step computed "
+                         "to DIR/features.npy (float64 [rows][16*C]; every row when that is at most "
+                         "60 MB, else a fixed seeded sample of rows, the same in every run)")
     ap.add_argument("--chunk-frames", type=int, default=1 << 23, help="stream workload chunk")
     ap.add_argument("--spacing", type=int, default=FRAMES_PER_EPOCH,
                     help="c3/c32: frames between markers (default 1000, the headline; < 687 makes "
@@ -93,9 +107,9 @@ def parse():
                          "exact: the reference's operation order, bit-identical")
     ap.add_argument("--alt-steps", type=int, default=10,
                     help="steps of a second, untimed-for-value pass in the other numerics mode "
-                         "(reported under 'alt_numerics'; 0 disables)")
+                         "(--full; reported under 'alt_numerics'; 0 disables)")
     ap.add_argument("--cpu-sample", type=int, default=500_000,
-                    help="epochs in the CPU-baseline sample (0 disables)")
+                    help="epochs in the CPU-baseline sample (--full; 0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0: every available host core (affinity, capped by a cgroup CPU quota)")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL feature gather legs")
@@ -296,9 +310,35 @@ def _stdout_to_stderr():
     os.dup2(2, 1)
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: under 64 MB with the .npy header
+
+
+def dump_rows(n, row_bytes):
+    """The feature rows --dump-outputs writes: every row when they fit DUMP_MAX_BYTES, else a
+    sample of as many rows as fit, drawn without replacement by a generator seeded with SEED and
+    sorted -- the same rows for the same n and row size in every run and every build."""
+    k = DUMP_MAX_BYTES // row_bytes
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, out):
+    """--dump-outputs DIR: DIR/features.npy, the float64 feature rows (torch [n][16*C], on the
+    device) that the caller of the timed path receives, or their dump_rows() sample."""
+    import torch
+    rows = dump_rows(out.shape[0], out.shape[1] * out.element_size())
+    if rows is not None:
+        out = out[torch.from_numpy(rows).to(out.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "features.npy"), out.cpu().numpy())
+
+
 def main():
     args = parse()
     _stdout_to_stderr()
+    if args.dump_outputs and args.workload not in ("c3", "c32"):
+        raise SystemExit("--dump-outputs is for the c3 and c32 workloads")
     import torch
     import torch.distributed as dist
 
@@ -351,7 +391,7 @@ def main():
         raise SystemExit("--spacing must be >= 100 frames")
     n_frames = sp * n + 2000
     ctx = fx.Context(dev.index, numerics=args.numerics)
-    meter = EnergyMeter(torch, dev.index)
+    meter = EnergyMeter(torch, dev.index) if args.full else None
     # A dedicated (non-null) torch stream shared with the context: the kernels run on it, so the
     # HIP events recorded on it bracket exactly the launches of the timed region.
     stream = torch.cuda.Stream(dev)
@@ -425,11 +465,15 @@ def main():
     if distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kernel_ms, step_ms = float(t[0]), float(t[1]), float(t[2])
-    energy = energy_leg(meter, torch, dev, step, step_ms, n, bytes_per_epoch(ct, C))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)  # `out` as the last timed step left it
+    # every leg below the headline runs under --full only
+    energy = (energy_leg(meter, torch, dev, step, step_ms, n, bytes_per_epoch(ct, C))
+              if args.full else None)
 
     # the other numerics mode, same buffers (reported beside the headline, not as value)
     alt = None
-    if args.alt_steps > 0:
+    if args.full and args.alt_steps > 0:
         other = "exact" if args.numerics != "exact" else "fma"
         ctx.set_numerics(other)
         step()
@@ -448,8 +492,10 @@ def main():
         torch.cuda.synchronize(dev)
 
     # sanity of the produced features (unit rows) -- outside the timed region
-    norms = torch.linalg.vector_norm(out, dim=1)
-    ok_norm = bool(torch.all(torch.isfinite(norms)) and torch.max(torch.abs(norms - 1)) < 1e-12)
+    ok_norm = None
+    if args.full:
+        norms = torch.linalg.vector_norm(out, dim=1)
+        ok_norm = bool(torch.all(torch.isfinite(norms)) and torch.max(torch.abs(norms - 1)) < 1e-12)
 
     line = None
     if rank == 0:
@@ -548,7 +594,7 @@ def main():
     # rank 0's host cores on a bounded sample of its own shard; at N > 1 after the gather legs,
     # so the timed extraction and gathers ran with every rank's host threads quiet
     cpu = None
-    if rank == 0 and args.cpu_sample > 0:
+    if rank == 0 and args.full and args.cpu_sample > 0:
         cpu = cpu_baseline(args, raw, out, ct, C, sp)
         if distributed:
             cpu["sample"] += (f"; rank 0 of {world}, after the gather legs (the other ranks idle "
@@ -578,13 +624,16 @@ def main():
 def guard_report(args, fx, dev, checked, rechecked, redone):
     """The fma conditioning guard over the timed steps: rows checked, rows that
     failed the a-priori test and went to the second stage (the row's measured max |x|), rows that
-    failed that too and were recomputed under EXACT; and the same on every marker of the
-    reference's two recordings (tests/golden/test-data, the repo's copies), outside the timed
-    region."""
+    failed that too and were recomputed under EXACT; and, under --full, the same on every marker
+    of the reference's two recordings (tests/golden/test-data, the repo's copies), outside the
+    timed region."""
     if args.numerics != "fma":
         return None
     rep = {"rows_checked": checked, "rows_rechecked": rechecked, "rows_recomputed": redone,
            "rate": (redone / checked) if checked else None, "reference_recordings": {}}
+    if not args.full:  # the recordings take a context and two runs of their own
+        rep["reference_recordings"] = None
+        return rep
     data = os.path.join(REPO, "tests", "golden", "test-data", "DoD")
     c = fx.Context(dev.index, numerics="fma")
     try:
@@ -955,7 +1004,7 @@ def bench_stream(args, rank, world, dev, dist):
     up_ms, down_ms = timed_copies(upload_only), timed_copies(download_only)
     del d_in, d_out
     cpu = None
-    if rank == 0 and args.cpu_sample > 0:
+    if rank == 0 and args.full and args.cpu_sample > 0:
         # the same recordings and marker grid on the host cores (BASELINE.json configs[4])
         cpu = cpu_baseline(args, torch.from_numpy(raw), torch.from_numpy(out), 3, 3,
                            sp=step_frames, first=int(pos[0]), n_epochs=n,
@@ -1037,7 +1086,7 @@ def bench_logreg(args, rank, world, dev, dist):
     per_iter = elapsed / steps / it
     bytes_iter = n * 48 * 8 + n * 8
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:
         from oracle import mllib_logreg as ref
         k = min(n, 100_000)
         Xh, yh = X[:k].cpu().numpy(), y[:k].cpu().numpy()

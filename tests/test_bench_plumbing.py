@@ -112,6 +112,74 @@ def test_gather_row_checksum_detects_misplaced_shards():
     assert bench.row_checksum(rows) != sums[2]
 
 
+def test_dump_rows_are_fixed_and_fit_64_mb():
+    """--dump-outputs: every row while they fit, else the same sorted sample in every run, under
+    64 MB (the headline's 1M x 48 doubles are 384 MB)."""
+    assert bench.dump_rows(1000, 48 * 8) is None
+    assert bench.dump_rows(bench.DUMP_MAX_BYTES // 384, 384) is None
+    rows = bench.dump_rows(1_000_000, 48 * 8)
+    assert rows.size * 384 <= bench.DUMP_MAX_BYTES < 64_000_000
+    assert rows.size == 156_250 and np.all(np.diff(rows) > 0)
+    assert 0 <= rows[0] and rows[-1] < 1_000_000
+    assert np.array_equal(rows, bench.dump_rows(1_000_000, 48 * 8))
+    assert bench.dump_rows(250_000, 512 * 8).size * 4096 <= bench.DUMP_MAX_BYTES
+
+
+def test_full_and_dump_are_off_by_default(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_steps_features(tmp_path):
+    """A plain run times exactly --steps steps, leaves the --full legs null, and --dump-outputs
+    holds the rows a caller of the timed path receives: within the fma bound (1e-9) of the
+    oracle on the same synthetic recording, and the same bits in a second run."""
+    import subprocess
+    import sys
+
+    import eeg_dataanalysispackage_amd as fx
+    import torch
+    from oracle import oracle
+
+    n = 3000
+    lines, dumps = [], []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                            "--steps", "3", "--warmup", "1", "--epochs", str(n),
+                            "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout))
+        assert sorted(os.listdir(tmp_path / d)) == ["features.npy"]
+        dumps.append(np.load(tmp_path / d / "features.npy"))
+    line, got = lines[0], dumps[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    # value = epochs / step time; ms_per_step is that time rounded to 4 decimals
+    assert abs(n / line["value"] * 1e3 - line["ms_per_step"]) <= 5.1e-5
+    assert line["cpu_baseline"] is None and "alt_numerics" not in line
+    assert line["roofline"]["whole_path"]["energy"] is None
+    assert line["config"]["unit_rows_check"] is None
+    assert line["config"]["guard"]["rows_checked"] == 3 * n
+    assert got.dtype == np.float64 and got.shape == (n, 48)
+    assert np.array_equal(got, dumps[1])
+    ctx = fx.Context(0)
+    try:
+        raw = torch.empty((1000 * n + 2000, 3), dtype=torch.int16, device="cuda:0")
+        ctx.synth_recording(raw, 3, bench.SEED)
+        ctx.synchronize()
+        host = raw.cpu().numpy()
+    finally:
+        ctx.close()
+    want = oracle.process_recording(host, [0, 1, 2], [0.1] * 3,
+                                    np.arange(1000, 1000 * (n + 1), 1000, dtype=np.int64))
+    assert np.max(np.abs(got - want)) <= 1e-9
+
+
 def test_live_energy_leg_arithmetic():
     """whole_path.energy: step energy from the accumulator over the untimed steps, the bound
     step_J / cap and its ratio to the timed step (a stand-in meter: 1.4 kW drawn, cap 1.4 kW)."""

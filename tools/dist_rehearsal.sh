@@ -12,17 +12,17 @@ OUT=gpurun_out/${TAG:-dist}
 mkdir -p "$OUT"
 echo "== force_dist (world 1, nccl)"; date
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-  --master-port 29531 bench.py --force-dist --steps 20 --warmup 10 --alt-steps 0 \
+  --master-port 29531 bench.py --full --force-dist --steps 20 --warmup 10 --alt-steps 0 \
   > "$OUT/bench_force_dist.json" 2> "$OUT/bench_force_dist.err" || { tail -30 "$OUT/bench_force_dist.err"; exit 1; }
 cat "$OUT/bench_force_dist.json"
 echo "== torchrun 2 ranks, same device"; date
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 10 --alt-steps 0 --same-device \
+  --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 10 --alt-steps 0 --same-device \
   --dist-backend gloo --no-gather > "$OUT/bench_torchrun2.json" 2> "$OUT/bench_torchrun2.err" || { tail -30 "$OUT/bench_torchrun2.err"; exit 1; }
 cat "$OUT/bench_torchrun2.json"
 echo "== torchrun 2 ranks, same device, gather legs over gloo (shard checksums)"; date
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29535 bench.py --gpus 2 --steps 5 --warmup 2 --alt-steps 0 --same-device \
+  --master-port 29535 bench.py --full --gpus 2 --steps 5 --warmup 2 --alt-steps 0 --same-device \
   --dist-backend gloo --epochs 20000 > "$OUT/bench_torchrun2_gather.json" 2> "$OUT/bench_torchrun2_gather.err" || { tail -30 "$OUT/bench_torchrun2_gather.err"; exit 1; }
 cat "$OUT/bench_torchrun2_gather.json"
 echo "== done"; date

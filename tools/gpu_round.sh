@@ -21,7 +21,7 @@ if [ "${TESTS:-1}" = "1" ]; then
 fi
 if [ "${BENCH:-1}" = "1" ]; then
   echo "== bench"; date
-  timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
   cat "$OUT/bench.json"
 fi
 cd /tmp
@@ -53,9 +53,9 @@ cd "$ROOT"
 for WL in ${EXTRA:-c32 stream dropin big}; do
   echo "== bench $WL"; date
   if [ "$WL" = "big" ]; then  # configs[2]: one rank's 8M-epoch shard (48 GB recording)
-    timeout -k 10 400 python bench.py --epochs 8000000 --steps 20 --warmup 10 --cpu-sample 0 --alt-steps 3 > "$OUT/bench_$WL.json" 2> "$OUT/bench_$WL.err" || { tail -30 "$OUT/bench_$WL.err"; exit 1; }
+    timeout -k 10 400 python bench.py --full --epochs 8000000 --steps 20 --warmup 10 --cpu-sample 0 --alt-steps 3 > "$OUT/bench_$WL.json" 2> "$OUT/bench_$WL.err" || { tail -30 "$OUT/bench_$WL.err"; exit 1; }
   else
-    timeout -k 10 400 python bench.py --workload $WL > "$OUT/bench_$WL.json" 2> "$OUT/bench_$WL.err" || { tail -30 "$OUT/bench_$WL.err"; exit 1; }
+    timeout -k 10 400 python bench.py --full --workload $WL > "$OUT/bench_$WL.json" 2> "$OUT/bench_$WL.err" || { tail -30 "$OUT/bench_$WL.err"; exit 1; }
   fi
   cat "$OUT/bench_$WL.json"
 done
