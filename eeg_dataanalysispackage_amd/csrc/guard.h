@@ -100,6 +100,34 @@ __device__ __forceinline__ bool guard_fails(double acc, double k2, double sum_x2
   return !(acc >= k2 * sum_x2);
 }
 
+// The range of a row's sum of squares in which the conditioning test says anything about the
+// normalised row.  The test bounds the features' differences; the norm is then taken from
+// squares, and both numerics round those: outside this range the two norms can differ by more
+// than the features do, so the row is recomputed under EXACT whatever the test says.
+//   upper end: a certified row's fma and EXACT sums of squares differ by a relative 3e-9 at
+//     most (the features by 0.5e-9 of the norm, <= 512 roundings of 2^-53), so while the fma
+//     sum is <= 2^1023 = DBL_MAX / 2 (1 - 2^-53) the EXACT sum is finite as well.  Above it
+//     (Inf included: Inf >= k2 * Inf certifies) one norm can be Inf, which turns every finite
+//     feature into 0.0, and the other finite.
+//   lower end: a square below DBL_MIN = 2^-1022 is rounded to a multiple of 2^-1074, an absolute
+//     error of 2^-1075 that the relative bounds do not cover; over <= 512 squares and both
+//     numerics that is 2^-1065.  With acc >= 2^-969 = DBL_MIN * 2^53 it is a relative 2^-96,
+//     nothing beside the sum's own 2^-53 roundings.  Below, the EXACT row itself drifts with
+//     the scale of its input (2^-530 * 50 N(0, 1): 5e-10 from the unscaled row), and only EXACT
+//     reproduces that.
+// acc = 0 with every X_c = 0 is the all-zero window: +-0 features and the reference's 0 / 0 = NaN
+// row under both numerics, certified; the caller keeps sum_x2 != 0 when a sample is nonzero.
+// Only caller-supplied doubles reach these ends (features_from_epochs_kernel).  The kernels
+// that decode a recording filter fp32 values: |x| <= 2 FLT_MAX = 2^129 and a gain of at most
+// (sum |h|)^6 = 2^6 over the six levels bound acc by 512 (2^6 * 2^129)^2 = 2^279, and a
+// certified row has acc >= k2 * X^2 >= 7e-5 * 2^-298 (X >= 2^-149, the smallest fp32) or
+// acc = sum_x2 = 0, so there the range test could never fail and is not made.
+constexpr double kGuardAccMin = 0x1p-969;
+constexpr double kGuardAccMax = 0x1p1023;
+__device__ __forceinline__ bool guard_acc_out_of_range(double acc, double sum_x2) {
+  return !((acc >= kGuardAccMin && acc <= kGuardAccMax) || (acc == 0.0 && sum_x2 == 0.0));
+}
+
 __device__ __forceinline__ void guard_slot_add(unsigned long long* slots, unsigned long long v) {
   atomicAdd(slots + (blockIdx.x & (kGuardSlots - 1)) * kGuardSlotWords, v);
 }

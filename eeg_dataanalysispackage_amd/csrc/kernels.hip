@@ -219,6 +219,8 @@ __device__ __forceinline__ void staged_features(Smp smp, GSmp gsmp, const int* s
                                   return (double)y;
                                 },
                                 C, lane));
+      } else if (fails && lane == 0) {
+        guard_count_rechecked(guard, 1);  // float32: the first test is the measured one
       }
       if (lane == 0) {
         sh[0] = rsqrt_nr(acc);
@@ -677,7 +679,8 @@ __global__ __launch_bounds__(64) void features_from_epochs_kernel(const double* 
                           },
                           lane & ~7, s, a6, d6);
       xm = group8_max(xm);
-      sx += xm * xm;
+      const double x2 = xm * xm;  // doubles below 2^-537 square to 0: keep X^2 != 0 (guard.h)
+      sx += x2 == 0.0 && xm != 0.0 ? 0x1p-1022 : x2;
     } else {
       const double* sig = win + el * kFeWin;
       double x[kIn];
@@ -714,13 +717,18 @@ __global__ __launch_bounds__(64) void features_from_epochs_kernel(const double* 
       }
     }
     norm[lane] = sqrt(acc);
-    fails = FAST && guard.total && guard_fails(acc, kGuardK2Collapsed, sx_row);
+    // caller-supplied doubles: also the rows whose norm the squares cannot carry (guard.h)
+    fails = FAST && guard.total && (guard_fails(acc, kGuardK2Collapsed, sx_row) ||
+                                    guard_acc_out_of_range(acc, sx_row));
   }
   if constexpr (FAST) {  // the guard's rare path: flagged rows recomputed under EXACT in place
     uint64_t flagged = __ballot(fails);
     if (flagged) {
       wave_sync();
-      if (lane == 0) guard_count_recomputed(guard, (unsigned long long)__popcll(flagged));
+      if (lane == 0) {  // the only test is the measured one: its failures count as both
+        guard_count_rechecked(guard, __popcll(flagged));
+        guard_count_recomputed(guard, (unsigned long long)__popcll(flagged));
+      }
       do {
         const int e = __ffsll((unsigned long long)flagged) - 1;
         const double* row = ep + (e0 + e) * C * (int64_t)row_stride + skip;

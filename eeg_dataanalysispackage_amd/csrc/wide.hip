@@ -276,6 +276,8 @@ __global__ __launch_bounds__(256) void window_wide_kernel(
                   return (double)y;
                 },
                 C, lane));
+      } else if (fails && lane == 0) {
+        guard_count_rechecked(guard, 1);  // float32: the first test is the measured one
       }
       if (lane == 0) {
         norm[m] = rsqrt_nr(acc);  // the reciprocal norm (multiplied below)

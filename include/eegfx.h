@@ -38,6 +38,11 @@
  * conditioning guard bounds each row's rounding difference from the EXACT row,
  * and the rows it cannot certify (features at rounding level, e.g. a window in the filters' null
  * space) are recomputed under EXACT on the device before the call's results are complete.
+ * Samples may hold any bit pattern and resolutions any float: NaN, +-Inf, -0.0, subnormal and
+ * overflowing fp32 products are carried through the decode as IEEE arithmetic carries them, and
+ * a row comes out as the reference computes it (a NaN or Inf in the window or the baseline gives
+ * an all-NaN row, an overflowing sum of squares 0.0 for every finite feature) under both
+ * numerics; the rows of the other epochs are unaffected.
  * Small host batches of eegfx_extract_features_f64 (the per-epoch drop-in) are computed under
  * EXACT in both settings (latency-bound; the guard's counters do not count them).
  */
@@ -120,8 +125,9 @@ int eegfx_ctx_guard_stats(eegfx_ctx* ctx, int64_t* rows_checked, int64_t* rows_r
                           int reset);
 /* The same counters, with the rows that failed the guard's a-priori test and went to its second
  * stage (the row's measured max |x|): rows_rechecked >= rows_recomputed, and
- * rows_rechecked - rows_recomputed rows were certified by the second stage.  rows_rechecked may be
- * NULL. */
+ * rows_rechecked - rows_recomputed rows were certified by the second stage.  For float32
+ * recordings and double epochs the only test is the measured one: a row that fails it counts in
+ * both.  rows_rechecked may be NULL. */
 int eegfx_ctx_guard_detail(eegfx_ctx* ctx, int64_t* rows_checked, int64_t* rows_rechecked,
                            int64_t* rows_recomputed, int reset);
 /* Opt-in resident server for the per-epoch drop-in (IFeatureExtraction.extractFeatures called
