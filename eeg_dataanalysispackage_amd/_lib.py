@@ -103,6 +103,9 @@ SIGNATURES = {
                                            c_int32, c_int32, c_int32, c_void_p, c_int]),
     "eegfx_process_recording": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
                                         c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int]),
+    "eegfx_process_recording_fe": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32,
+                                           c_void_p, c_void_p, c_int32, c_void_p, c_int64,
+                                           c_int32, c_int32, c_int32, c_int32, c_void_p, c_int]),
     "eegfx_process_recording_epochs": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32,
                                                c_void_p, c_void_p, c_int32, c_void_p, c_int64,
                                                c_void_p, c_void_p, c_int]),

@@ -211,7 +211,10 @@ class Context:
 
     def extract_features(self, epochs, name=8, epoch_size=512, skip=175, feature_size=16,
                          out=None):
-        """Batched WaveletTransform.extractFeatures over epochs double[n][C][750]."""
+        """Batched WaveletTransform.extractFeatures over epochs double[n][C][750]: rows
+        [n][C*feature_size], feature_size <= 512 (a channel's features are the first feature_size
+        coefficients of its pyramid [a6 d6 d5 d4 d3 d2 d1]; sizes above 16 are EXACT under both
+        numerics)."""
         epochs = _contig(epochs, np.float64)
         shape = tuple(epochs.shape)
         if len(shape) != 3 or shape[2] != _lib.POSTSTIMULUS:
@@ -225,8 +228,12 @@ class Context:
                    name, epoch_size, skip, feature_size, ptr(out), mem)
         return out
 
-    def process_recording(self, raw, n_channels_total: int, cols, res, pos, out=None):
-        """Fused hot path: raw recording + marker positions -> dwt-8 features [n][16*C]."""
+    def process_recording(self, raw, n_channels_total: int, cols, res, pos, out=None, skip=175,
+                          feature_size=16):
+        """Fused hot path: raw recording + marker positions -> dwt-8 features
+        [n][feature_size*C].  Another skip or feature size than WaveletTransform(8, 512, 175,
+        16)'s goes through eegfx_process_recording_fe (feature sizes up to 512: the first
+        feature_size coefficients of each channel's pyramid, EXACT under both numerics)."""
         cols_a, res_a = self._sel(cols, res)
         raw = _raw(raw)
         fmt = _fmt(raw)
@@ -235,11 +242,17 @@ class Context:
         n = _numel(pos)
         C = len(cols_a)
         if out is None:
-            out = _empty_like_mem(raw, (n, 16 * C), "float64")
-        _check_out(out, (n, 16 * C))
+            out = _empty_like_mem(raw, (n, max(feature_size, 0) * C), "float64")
+        _check_out(out, (n, max(feature_size, 0) * C))
         mem = _mem(raw, pos, out)
-        self._call(mem, raw, lib().eegfx_process_recording, self.handle, ptr(raw), fmt, n_frames,
-                   n_channels_total, ptr(cols_a), ptr(res_a), C, ptr(pos), n, ptr(out), mem)
+        if skip == 175 and feature_size == 16:
+            self._call(mem, raw, lib().eegfx_process_recording, self.handle, ptr(raw), fmt,
+                       n_frames, n_channels_total, ptr(cols_a), ptr(res_a), C, ptr(pos), n,
+                       ptr(out), mem)
+        else:
+            self._call(mem, raw, lib().eegfx_process_recording_fe, self.handle, ptr(raw), fmt,
+                       n_frames, n_channels_total, ptr(cols_a), ptr(res_a), C, ptr(pos), n, 8, 512,
+                       skip, feature_size, ptr(out), mem)
         return out
 
     def process_recording_epochs(self, raw, n_channels_total: int, cols, res, pos, out=None,

@@ -184,11 +184,17 @@ void check_fe_params(int C, int name, int epoch_size, int skip, int feature_size
     fail(EEGFX_ERANGE, "window [%d, %d) outside the %d-sample epoch", skip, skip + epoch_size,
          EEGFX_POSTSTIMULUS);
   if (feature_size <= 0) fail(EEGFX_EINVAL, "feature size %d", feature_size);
-  if (name != EEGFX_DWT8_NAME || epoch_size != EEGFX_DWT8_EPOCH_SIZE || feature_size > 16)
+  if (name != EEGFX_DWT8_NAME || epoch_size != EEGFX_DWT8_EPOCH_SIZE ||
+      feature_size > EEGFX_DWT8_MAX_FEATURE_SIZE)
     fail(EEGFX_ENOTSUP,
-         "no kernel for wavelet %d / epoch size %d / feature size %d (supported: dwt-8, 512, <=16)",
+         "no kernel for wavelet %d / epoch size %d / feature size %d (supported: dwt-8, 512, <=512)",
          name, epoch_size, feature_size);
 }
+
+// Feature sizes past a6 ++ d6 take the full-pyramid kernels (pyramid.hip): EXACT under both
+// numerics settings, outside the fma guard and its counters, and never the per-epoch kernel or
+// the resident server (mailbox_request packs nfeat - 1 into 5 bits).
+bool wide_features(int feature_size) { return feature_size > EEGFX_DWT8_FEATURE_SIZE; }
 
 }  // namespace
 
@@ -1249,7 +1255,8 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
       const size_t row_w = sizeof(double) * EEGFX_DWT8_EPOCH_SIZE;
       const size_t row_p = sizeof(double) * EEGFX_POSTSTIMULUS;
       const uint8_t* src = (const uint8_t*)epochs + sizeof(double) * (size_t)skip;
-      if ((size_t)n * C * row_w <= kZeroCopyBytes && features_small_supported(C)) {
+      if ((size_t)n * C * row_w <= kZeroCopyBytes && features_small_supported(C) &&
+          !wide_features(feature_size)) {
         // Small batches (a single epoch above all): latency, not bandwidth.  The window rows are
         // packed into a pinned, device-mapped buffer by the calling thread and the kernel
         // (features_small_kernel) reads them -- and writes the rows -- across the host link
@@ -1304,16 +1311,21 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
       const size_t chunk_bytes = (size_t)std::min<int64_t>(n, kChunk) * C * row_w;
       uint8_t* dwin = (uint8_t*)ctx->scratch.get(chunk_bytes);
       double* d_out = (double*)ctx->out.get(out_bytes);
-      const Guard g = ctx->guard_for(n);
+      const bool wide = wide_features(feature_size);
+      const Guard g = wide ? Guard{nullptr, nullptr, nullptr} : ctx->guard_for(n);
       ctx->tic();
       for (int64_t e0 = 0; e0 < n; e0 += kChunk) {
         const int64_t m = std::min<int64_t>(kChunk, n - e0);
         HIP_CHECK(hipMemcpy2DAsync(dwin, row_w, src + (size_t)e0 * C * row_p, row_p, row_w,
                                    (size_t)(m * C), hipMemcpyHostToDevice, ctx->stream));
         double* rows = d_out + e0 * C * feature_size;
-        HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)dwin, m, C, 0,
-                                              feature_size, ctx->numerics != EEGFX_EXACT, rows,
-                                              EEGFX_DWT8_EPOCH_SIZE, g));
+        if (wide)
+          HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)dwin, m, C, 0,
+                                               feature_size, rows, EEGFX_DWT8_EPOCH_SIZE));
+        else
+          HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)dwin, m, C, 0,
+                                                feature_size, ctx->numerics != EEGFX_EXACT, rows,
+                                                EEGFX_DWT8_EPOCH_SIZE, g));
       }
       ctx->toc(0);
       HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1322,12 +1334,19 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
     }
     const double* d_in = (const double*)stage_in(ctx, ctx->scratch, epochs, in_bytes, mem);
     double* d_out = mem == EEGFX_MEM_DEVICE ? out : (double*)ctx->out.get(out_bytes);
-    const Guard g = ctx->guard_for(n);
-    ctx->tic();
-    HIP_CHECK(launch_features_from_epochs(ctx->stream, d_in, n, C, skip, feature_size,
-                                          ctx->numerics != EEGFX_EXACT, d_out, EEGFX_POSTSTIMULUS,
-                                          g));
-    ctx->toc(0);
+    if (wide_features(feature_size)) {
+      ctx->tic();
+      HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, d_in, n, C, skip, feature_size, d_out,
+                                           EEGFX_POSTSTIMULUS));
+      ctx->toc(0);
+    } else {
+      const Guard g = ctx->guard_for(n);
+      ctx->tic();
+      HIP_CHECK(launch_features_from_epochs(ctx->stream, d_in, n, C, skip, feature_size,
+                                            ctx->numerics != EEGFX_EXACT, d_out,
+                                            EEGFX_POSTSTIMULUS, g));
+      ctx->toc(0);
+    }
     if (mem == EEGFX_MEM_HOST) {
       HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
       ctx->drain();
@@ -1354,6 +1373,53 @@ int eegfx_process_recording(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_
     const int64_t* d_pos = (const int64_t*)stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
     double* d_out = mem == EEGFX_MEM_DEVICE ? features : (double*)ctx->out.get(out_bytes);
     run_features_from_raw(ctx, d_raw, fmt, n_frames, ct, sel, C, d_pos, n, d_out);
+    if (mem == EEGFX_MEM_HOST) {
+      HIP_CHECK(hipMemcpyAsync(features, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+      ctx->drain();
+    }
+  });
+}
+
+int eegfx_process_recording_fe(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
+                               int32_t ct, const int32_t* cols, const float* res, int32_t C,
+                               const int64_t* pos, int64_t n, int32_t name, int32_t epoch_size,
+                               int32_t skip, int32_t feature_size, double* features, int mem) {
+  if (name == EEGFX_DWT8_NAME && epoch_size == EEGFX_DWT8_EPOCH_SIZE && skip == EEGFX_DWT8_SKIP &&
+      feature_size == EEGFX_DWT8_FEATURE_SIZE)
+    return eegfx_process_recording(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, features,
+                                   mem);
+  return guarded([&] {
+    if (!ctx) fail(EEGFX_EINVAL, "null context");
+    check_mem(mem);
+    if (fmt != EEGFX_INT_16 && fmt != EEGFX_IEEE_FLOAT_32) fail(EEGFX_EINVAL, "format %d", fmt);
+    if (n_frames < 0 || n < 0 || ct < 1) fail(EEGFX_EINVAL, "negative size");
+    if (n > 0 && (!raw || !pos || !features)) fail(EEGFX_EINVAL, "null buffer");
+    const ChanSel sel = make_sel(cols, res, C, ct);
+    check_fe_params(C, name, epoch_size, skip, feature_size);
+    if (mem == EEGFX_MEM_HOST) check_positions(pos, n, n_frames);
+    if (n == 0) return;
+    ctx->activate();
+    const size_t raw_bytes = (size_t)n_frames * ct * (fmt == EEGFX_INT_16 ? 2 : 4);
+    const size_t out_bytes = sizeof(double) * (size_t)n * C * feature_size;
+    const void* d_raw = stage_in(ctx, ctx->raw, raw, raw_bytes, mem);
+    const int64_t* d_pos = (const int64_t*)stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
+    double* d_out = mem == EEGFX_MEM_DEVICE ? features : (double*)ctx->out.get(out_bytes);
+    // The two passes: the epochs into scratch memory, then the rows from them.  (A fused raw ->
+    // rows pyramid kernel measured slower than this at feature size 512: DESIGN.md 5.4.1.)
+    double* ep = (double*)ctx->scratch.get(sizeof(double) * (size_t)n * C * EEGFX_POSTSTIMULUS);
+    ctx->tic();
+    HIP_CHECK(launch_cut_epochs(ctx->stream, d_raw, fmt, n_frames, ct, sel, C, d_pos, n, ep,
+                                ctx->fused.get(fused_scratch_bytes(n, C)), ctx->err_dev));
+    if (wide_features(feature_size)) {
+      HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, ep, n, C, skip, feature_size, d_out,
+                                           EEGFX_POSTSTIMULUS));
+    } else {
+      const Guard g = ctx->guard_for(n);
+      HIP_CHECK(launch_features_from_epochs(ctx->stream, ep, n, C, skip, feature_size,
+                                            ctx->numerics != EEGFX_EXACT, d_out,
+                                            EEGFX_POSTSTIMULUS, g));
+    }
+    ctx->toc(0);
     if (mem == EEGFX_MEM_HOST) {
       HIP_CHECK(hipMemcpyAsync(features, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
       ctx->drain();
@@ -1875,11 +1941,17 @@ int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int
       return;
     }
     double* d_out = (double*)ctx->out.get(out_bytes);
-    const Guard g = ctx->guard_for(odp->n_epochs);
-    HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)odp->d_epochs,
-                                          odp->n_epochs, 3, skip, feature_size,
-                                          ctx->numerics != EEGFX_EXACT, d_out, EEGFX_POSTSTIMULUS,
-                                          g));
+    if (wide_features(feature_size)) {
+      HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)odp->d_epochs,
+                                           odp->n_epochs, 3, skip, feature_size, d_out,
+                                           EEGFX_POSTSTIMULUS));
+    } else {
+      const Guard g = ctx->guard_for(odp->n_epochs);
+      HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)odp->d_epochs,
+                                            odp->n_epochs, 3, skip, feature_size,
+                                            ctx->numerics != EEGFX_EXACT, d_out,
+                                            EEGFX_POSTSTIMULUS, g));
+    }
     HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     ctx->drain();
   });

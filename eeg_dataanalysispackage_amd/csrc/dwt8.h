@@ -963,6 +963,60 @@ __device__ __forceinline__ void dwt8_cascade(const double (&x)[kIn], double* xch
   d6 = fir10<FAST, true>(a5);
 }
 
+// The full pyramid under EXACT numerics (feature sizes 17..512, pyramid.hip).  The in-place
+// layout the reference copies its first FEATURE_SIZE coefficients from is
+//     [a6(8) d6(8) d5(16) d4(32) d3(64) d2(128) d1(256)]
+// and at each level the lane already holds the inputs of its low-pass outputs, so the high-pass
+// outputs come from the same registers (fir10<false, true>).  Lane s owns
+//     d1 [32s, 32s+32) -> 256 + 32s + i     d2 [16s, 16s+16) -> 128 + 16s + i
+//     d3 [8s, 8s+8)    ->  64 +  8s + i     d4 [4s, 4s+4)    ->  32 +  4s + i
+//     d5 [2s, 2s+2)    ->  16 +  2s + i     a6 -> s,  d6 -> 8 + s
+// Every detail is handed to emit(index, value) as it is produced (the caller puts it in LDS), so
+// none stays live.  DMIN = the lowest level whose details the feature size reaches (pyramid_dmin):
+// the others are not formed (d1 alone doubles the multiply-adds of the transform).
+__host__ __device__ constexpr int pyramid_dmin(int nfeat) {
+  return nfeat > 256 ? 1 : nfeat > 128 ? 2 : nfeat > 64 ? 3 : nfeat > 32 ? 4 : 5;
+}
+
+// One level: out[i] = low-pass output i of the lane's slice, i < N; DET: its high-pass twin goes
+// to emit(row0 + i, .).
+template <int N, bool DET, typename Emit>
+__device__ __forceinline__ void pyramid_band(const double* in, double* out, int row0, Emit emit) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    out[i] = fir10<false, false>(in + 2 * i);
+    if constexpr (DET) emit(row0 + i, fir10<false, true>(in + 2 * i));
+  }
+}
+
+// Level 1 from the 72 samples of the lane (slice + halo); a1 receives the slice and its halo.
+template <int DMIN, bool SHFL, typename Emit>
+__device__ __forceinline__ void dwt8_pyramid_level1(const double (&x)[kIn], double* xch, int gbase,
+                                                    int s, double (&a1)[40], Emit emit) {
+  pyramid_band<32, DMIN <= 1>(x, a1, 256 + 32 * s, emit);
+  halo<32, SHFL>(a1, xch, gbase, s);
+}
+
+// Levels 2..6 from the level-1 slice and halo: d2..d5 as DMIN asks, then a6[s] and d6[s].
+template <int DMIN, bool SHFL, typename Emit>
+__device__ __forceinline__ void dwt8_pyramid_levels2to6(double (&a1)[40], double* xch, int gbase,
+                                                        int s, double& a6, double& d6, Emit emit) {
+  double a2[16 + 8];
+  pyramid_band<16, DMIN <= 2>(a1, a2, 128 + 16 * s, emit);
+  halo<16, SHFL>(a2, xch, gbase, s);
+  double a3[8 + 8];
+  pyramid_band<8, DMIN <= 3>(a2, a3, 64 + 8 * s, emit);
+  halo<8, SHFL>(a3, xch, gbase, s);
+  double a4[4 + 8];
+  pyramid_band<4, DMIN <= 4>(a3, a4, 32 + 4 * s, emit);
+  halo<4, SHFL>(a4, xch, gbase, s);
+  double a5[2 + 8];
+  pyramid_band<2, DMIN <= 5>(a4, a5, 16 + 2 * s, emit);
+  halo<2, SHFL>(a5, xch, gbase, s);
+  a6 = fir10<false, false>(a5);
+  d6 = fir10<false, true>(a5);
+}
+
 }  // namespace dev
 }  // namespace eegfx
 

@@ -1,4 +1,5 @@
-// launch.h -- host-side launchers of the gfx950 kernels (kernels.hip, fused.hip).
+// launch.h -- host-side launchers of the gfx950 kernels (kernels.hip, fused.hip, wide.hip,
+// pyramid.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -108,6 +109,11 @@ hipError_t launch_window_wide(hipStream_t st, const void* raw, int fmt, int64_t 
                               const ChanSel& sel, int C, const int64_t* pos, int64_t n, bool fast,
                               const void* scratch, double* out, const Guard& guard,
                               bool track = false);
+
+// The full pyramid (pyramid.hip): feature sizes 17..512, EXACT under both numerics settings, no
+// guard.  ep / row_stride / skip as launch_features_from_epochs; out = double[n][C * nfeat].
+hipError_t launch_pyramid_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
+                                      int nfeat, double* out, int row_stride);
 
 // guard.hip: the EXACT recomputation of the rows the generic any-layout kernels flagged (no-op
 // when g.count is null; launch_window_wide issues it).  raw: the same recording / positions /

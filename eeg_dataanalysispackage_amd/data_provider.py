@@ -72,7 +72,8 @@ class OffLineDataProvider:
         return pos[:n], fid[:n]
 
     def getFeatures(self, name=8, epoch_size=512, skip=175, feature_size=16) -> np.ndarray:
-        """fe=dwt-8 features of the resident epochs, computed on the device."""
+        """fe=dwt-8 features of the resident epochs, computed on the device: [n][3*feature_size],
+        feature_size <= 512 (the first feature_size coefficients of each channel's pyramid)."""
         n = self.num_epochs()
         out = np.empty((n, 3 * feature_size), dtype=np.float64)
         if n:

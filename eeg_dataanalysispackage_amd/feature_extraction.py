@@ -4,8 +4,14 @@ Mirrors FeatureExtraction/IFeatureExtraction.java:27-35 and WaveletTransform.jav
 constructor ``WaveletTransform(name, epochSize, skipSamples, featureSize)`` (:82-87), the
 validating setters (:160-212) raising ``ValueError`` where Java raises
 IllegalArgumentException, ``getFeatureDimension()`` = FEATURE_SIZE * 3 / 1 (:150-152), and
-``extractFeatures(epoch)`` for one ``double[3][750]`` epoch returning a fresh 48-vector.
+``extractFeatures(epoch)`` for one ``double[3][750]`` epoch returning a fresh
+``3 * FEATURE_SIZE``-vector (48 for fe=dwt-8).
 ``extractFeaturesBatch`` is the batched form the GPU is built for (one launch per batch).
+
+Feature sizes up to 512 run on the device: each channel contributes the first FEATURE_SIZE
+coefficients of the in-place pyramid ``[a6(8) d6(8) d5(16) d4(32) d3(64) d2(128) d1(256)]`` of
+its 512-sample window (:126-137, :205-212).  ``setFeatureSize`` accepts up to 1024 as the Java
+setter does; sizes above 512 fail at the first call with EEGFX_ENOTSUP (-7).
 """
 from __future__ import annotations
 

@@ -44,7 +44,8 @@
  * an all-NaN row, an overflowing sum of squares 0.0 for every finite feature) under both
  * numerics; the rows of the other epochs are unaffected.
  * Small host batches of eegfx_extract_features_f64 (the per-epoch drop-in) are computed under
- * EXACT in both settings (latency-bound; the guard's counters do not count them).
+ * EXACT in both settings (latency-bound; the guard's counters do not count them), and so are
+ * feature sizes above 16 on every path (the full pyramid; see eegfx_extract_features_f64).
  */
 #ifndef EEGFX_H_
 #define EEGFX_H_
@@ -75,6 +76,7 @@ extern "C" {
 #define EEGFX_DWT8_EPOCH_SIZE 512
 #define EEGFX_DWT8_SKIP 175
 #define EEGFX_DWT8_FEATURE_SIZE 16
+#define EEGFX_DWT8_MAX_FEATURE_SIZE 512 /* the whole pyramid of a 512-sample window */
 
 /* sample formats of BrainVision BinaryFormat= */
 #define EEGFX_INT_16 0
@@ -235,7 +237,15 @@ int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n
  * WaveletTransform(name, epoch_size, skip, feature_size).extractFeatures for each
  * epochs[i] = double[C][750] (WaveletTransform.java:107-141).  out = double[n][C*feature_size],
  * each row L2-normalised (SignalProcessing.java:38-52).  Supported: name 8 with epoch_size 512,
- * skip + 512 <= 750 and feature_size <= 16 (the coefficients a6 ++ d6), C <= 64. */
+ * skip + 512 <= 750, feature_size <= 512 (EEGFX_DWT8_MAX_FEATURE_SIZE) and C <= 64.  A channel's
+ * features are the first feature_size coefficients of the in-place pyramid of its 512-sample
+ * window (WaveletTransform.java:126-137, :205-212),
+ *     [a6(8) d6(8) d5(16) d4(32) d3(64) d2(128) d1(256)]
+ * so feature_size <= 16 takes a6 ++ d6 and every larger size adds detail bands, coarsest first.
+ * feature_size > 16 is computed under EEGFX_EXACT in both numerics settings (the fma guard has
+ * no bound for the detail bands; its counters do not count these rows) and always by a launch:
+ * such calls leave a resident server (eegfx_ctx_set_mailbox) and its staging alone.
+ * feature_size > 512 and any other name or epoch_size return EEGFX_ENOTSUP. */
 int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, int32_t C,
                                int32_t name, int32_t epoch_size, int32_t skip,
                                int32_t feature_size, double* out, int mem);
@@ -247,6 +257,24 @@ int eegfx_process_recording(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_
                             int32_t n_channels_total, const int32_t* cols, const float* res,
                             int32_t C, const int64_t* pos, int64_t n_epochs, double* features,
                             int mem);
+
+/* eegfx_process_recording for any WaveletTransform(name, epoch_size, skip, feature_size) that
+ * eegfx_extract_features_f64 supports: features = double[n][C * feature_size], equal to
+ * eegfx_cut_epochs_f64 followed by eegfx_extract_features_f64 with the same parameters (bit for
+ * bit under EEGFX_EXACT; feature_size > 16 is EXACT in both settings, see there).  With
+ * (8, 512, 175, 16) it is eegfx_process_recording itself, the fused kernels.  Every other
+ * combination cuts the epochs into the context's scratch memory (6,000 C bytes per epoch) and
+ * extracts from them on the device, for every layout eegfx_cut_epochs_f64 accepts: a fused
+ * kernel for wide rows measured slower than the two passes at feature_size 512 (DESIGN.md
+ * 5.4.1).  Positions are validated as in
+ * eegfx_process_recording: host positions fail the call with EEGFX_ERANGE, device positions are
+ * reported by the next synchronising call.  skip + 512 > 750 is EEGFX_ERANGE, feature_size > 512
+ * or another name / epoch_size EEGFX_ENOTSUP. */
+int eegfx_process_recording_fe(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
+                               int32_t n_channels_total, const int32_t* cols, const float* res,
+                               int32_t C, const int64_t* pos, int64_t n_epochs, int32_t name,
+                               int32_t epoch_size, int32_t skip, int32_t feature_size,
+                               double* features, int mem);
 
 /* getData() and extractFeatures in one pass (OffLineDataProvider.java:216-233 materialises the
  * epochs, LogisticRegressionClassifier.java:87-90 then maps WaveletTransform.extractFeatures over
