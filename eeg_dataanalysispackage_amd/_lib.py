@@ -99,6 +99,13 @@ SIGNATURES = {
                                    c_void_p, c_void_p, POINTER(c_int64)]),
     "eegfx_cut_epochs_f64": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
                                      c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int]),
+    "eegfx_cut_epochs_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
+                                     c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int]),
+    "eegfx_extract_features_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                           c_int32, c_int32, c_int32, c_void_p, c_int]),
+    "eegfx_process_recording_epochs_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32,
+                                                   c_void_p, c_void_p, c_int32, c_void_p, c_int64,
+                                                   c_void_p, c_void_p, c_int]),
     "eegfx_extract_features_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                            c_int32, c_int32, c_int32, c_void_p, c_int]),
     "eegfx_process_recording": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
@@ -149,6 +156,7 @@ SIGNATURES = {
     "eegfx_odp_error": (c_char_p, [c_void_p]),
     "eegfx_odp_num_epochs": (c_int64, [c_void_p]),
     "eegfx_odp_get_data": (c_int, [c_void_p, c_void_p]),
+    "eegfx_odp_get_data_f32": (c_int, [c_void_p, c_void_p]),
     "eegfx_odp_get_labels": (c_int, [c_void_p, c_void_p]),
     "eegfx_odp_get_positions": (c_int, [c_void_p, c_void_p, c_void_p]),
     "eegfx_odp_get_features": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

@@ -52,6 +52,15 @@ def _contig(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def _epoch_dtype(dtype) -> str:
+    """The element type of an epoch buffer: "float64" (the reference's double[][]) or "float32"
+    (the fp32 values it widens, eegfx_*_f32)."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"epochs are float64 or float32, got {dt}")
+    return dt.name
+
+
 def _check_out(out, shape, dtype="float64"):
     """A caller-supplied output: right shape, dtype and contiguity (the kernels write it raw)."""
     if tuple(out.shape) != tuple(shape):
@@ -191,9 +200,12 @@ class Context:
             raise ValueError("cols and res must be 1-D of equal length")
         return cols_a, res_a
 
-    def cut_epochs(self, raw, n_channels_total: int, cols, res, pos, out=None):
+    def cut_epochs(self, raw, n_channels_total: int, cols, res, pos, out=None, dtype=np.float64):
         """Raw multiplexed recording (int16 or float32, n_frames x n_channels_total) ->
-        baseline-corrected epochs double[n][C][750] (OffLineDataProvider.java:216-233)."""
+        baseline-corrected epochs double[n][C][750] (OffLineDataProvider.java:216-233).
+        dtype=np.float32: float[n][C][750], the fp32 values the double epochs widen
+        (eegfx_cut_epochs_f32); `out` must have the dtype asked for."""
+        ename = _epoch_dtype(dtype)
         cols_a, res_a = self._sel(cols, res)
         raw = _raw(raw)
         fmt = _fmt(raw)
@@ -202,10 +214,11 @@ class Context:
         n = _numel(pos)
         C = len(cols_a)
         if out is None:
-            out = _empty_like_mem(raw, (n, C, _lib.POSTSTIMULUS), "float64")
-        _check_out(out, (n, C, _lib.POSTSTIMULUS))
+            out = _empty_like_mem(raw, (n, C, _lib.POSTSTIMULUS), ename)
+        _check_out(out, (n, C, _lib.POSTSTIMULUS), ename)
         mem = _mem(raw, pos, out)
-        self._call(mem, raw, lib().eegfx_cut_epochs_f64, self.handle, ptr(raw), fmt, n_frames,
+        fn = lib().eegfx_cut_epochs_f64 if ename == "float64" else lib().eegfx_cut_epochs_f32
+        self._call(mem, raw, fn, self.handle, ptr(raw), fmt, n_frames,
                    n_channels_total, ptr(cols_a), ptr(res_a), C, ptr(pos), n, ptr(out), mem)
         return out
 
@@ -225,6 +238,32 @@ class Context:
         _check_out(out, (n, C * feature_size))
         mem = _mem(epochs, out)
         self._call(mem, epochs, lib().eegfx_extract_features_f64, self.handle, ptr(epochs), n, C,
+                   name, epoch_size, skip, feature_size, ptr(out), mem)
+        return out
+
+    def extract_features_f32(self, epochs, name=8, epoch_size=512, skip=175, feature_size=16,
+                             out=None):
+        """extract_features over float32 epochs float[n][C][750] (eegfx_extract_features_f32):
+        the rows of extract_features on the same epochs widened to double, bit for bit.  Host
+        arrays must already be float32 (doubles are never narrowed silently), device tensors
+        torch.float32; any 4-byte-aligned view will do."""
+        if _is_device(epochs):
+            epochs = _contig(epochs, np.float32)
+        else:
+            epochs = np.asarray(epochs)
+            if epochs.dtype != np.float32:
+                raise ValueError(f"extract_features_f32 takes float32 epochs, got {epochs.dtype} "
+                                 "(use extract_features for doubles)")
+            epochs = np.ascontiguousarray(epochs)
+        shape = tuple(epochs.shape)
+        if len(shape) != 3 or shape[2] != _lib.POSTSTIMULUS:
+            raise ValueError(f"epochs must be [n][C][750], got {shape}")
+        n, C = shape[0], shape[1]
+        if out is None:
+            out = _empty_like_mem(epochs, (n, C * feature_size), "float64")
+        _check_out(out, (n, C * feature_size))
+        mem = _mem(epochs, out)
+        self._call(mem, epochs, lib().eegfx_extract_features_f32, self.handle, ptr(epochs), n, C,
                    name, epoch_size, skip, feature_size, ptr(out), mem)
         return out
 
@@ -256,9 +295,12 @@ class Context:
         return out
 
     def process_recording_epochs(self, raw, n_channels_total: int, cols, res, pos, out=None,
-                                 epochs_out=None):
+                                 epochs_out=None, epochs_dtype=np.float64):
         """getData() and extractFeatures in one pass (eegfx_process_recording_epochs): returns
-        (features [n][16*C], epochs [n][C][750]), each equal to its own call."""
+        (features [n][16*C], epochs [n][C][750]), each equal to its own call.
+        epochs_dtype=np.float32: the epochs as float32 (eegfx_process_recording_epochs_f32), the
+        features unchanged; `epochs_out` must have the dtype asked for."""
+        ename = _epoch_dtype(epochs_dtype)
         cols_a, res_a = self._sel(cols, res)
         raw = _raw(raw)
         fmt = _fmt(raw)
@@ -269,11 +311,13 @@ class Context:
         if out is None:
             out = _empty_like_mem(raw, (n, 16 * C), "float64")
         if epochs_out is None:
-            epochs_out = _empty_like_mem(raw, (n, C, _lib.POSTSTIMULUS), "float64")
+            epochs_out = _empty_like_mem(raw, (n, C, _lib.POSTSTIMULUS), ename)
         _check_out(out, (n, 16 * C))
-        _check_out(epochs_out, (n, C, _lib.POSTSTIMULUS))
+        _check_out(epochs_out, (n, C, _lib.POSTSTIMULUS), ename)
         mem = _mem(raw, pos, out, epochs_out)
-        self._call(mem, raw, lib().eegfx_process_recording_epochs, self.handle, ptr(raw), fmt,
+        fn = (lib().eegfx_process_recording_epochs if ename == "float64"
+              else lib().eegfx_process_recording_epochs_f32)
+        self._call(mem, raw, fn, self.handle, ptr(raw), fmt,
                    n_frames, n_channels_total, ptr(cols_a), ptr(res_a), C, ptr(pos), n, ptr(out),
                    ptr(epochs_out), mem)
         return out, epochs_out

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <thread>
+#include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -734,9 +735,11 @@ void run_features_from_raw(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n_f
 }
 
 // raw -> epochs + features (device pointers): the one-pass kernels when the layout fits them,
-// else the cut pass followed by the batch extract over the rows it wrote.
+// else the cut pass followed by the batch extract over the rows it wrote.  E: double or float epochs
+// (eegfx_process_recording_epochs / _f32): the same kernels, the same rows in `feat`.
+template <typename E>
 void run_epochs_and_features(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n_frames, int ct,
-                             const ChanSel& sel, int C, const int64_t* pos, int64_t n, double* ep,
+                             const ChanSel& sel, int C, const int64_t* pos, int64_t n, E* ep,
                              double* feat) {
   const bool fast = ctx->numerics != EEGFX_EXACT;
   const Guard g = ctx->guard_for(n);
@@ -1205,9 +1208,18 @@ int eegfx_read_raw(eegfx_ctx* ctx, const char* vhdr_path, const char* eeg_path, 
   });
 }
 
-int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
-                         int32_t ct, const int32_t* cols, const float* res, int32_t C,
-                         const int64_t* pos, int64_t n, double* epochs_out, int mem) {
+}  // extern "C"
+
+// The entries that carry epochs exist for two element types (double[n][C][750], the reference's
+// interface, and float[n][C][750], the fp32 values it widens): one implementation each, templated
+// on the element type E, behind the extern "C" pairs that follow.
+namespace {
+
+// eegfx_cut_epochs_f64 / _f32: E is the element type of epochs_out.
+template <typename E>
+int cut_epochs_api(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames, int32_t ct,
+                   const int32_t* cols, const float* res, int32_t C, const int64_t* pos, int64_t n,
+                   E* epochs_out, int mem) {
   return guarded([&] {
     if (!ctx) fail(EEGFX_EINVAL, "null context");
     check_mem(mem);
@@ -1219,10 +1231,10 @@ int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n
     if (n == 0) return;
     ctx->activate();
     const size_t raw_bytes = (size_t)n_frames * ct * (fmt == EEGFX_INT_16 ? 2 : 4);
-    const size_t out_bytes = sizeof(double) * (size_t)n * C * EEGFX_POSTSTIMULUS;
+    const size_t out_bytes = sizeof(E) * (size_t)n * C * EEGFX_POSTSTIMULUS;
     const void* d_raw = stage_in(ctx, ctx->raw, raw, raw_bytes, mem);
     const int64_t* d_pos = (const int64_t*)stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
-    double* d_out = mem == EEGFX_MEM_DEVICE ? epochs_out : (double*)ctx->out.get(out_bytes);
+    E* d_out = mem == EEGFX_MEM_DEVICE ? epochs_out : (E*)ctx->out.get(out_bytes);
     ctx->tic();
     HIP_CHECK(launch_cut_epochs(ctx->stream, d_raw, fmt, n_frames, ct, sel, C, d_pos, n, d_out,
                                 ctx->fused.get(fused_scratch_bytes(n, C)), ctx->err_dev));
@@ -1234,9 +1246,12 @@ int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n
   });
 }
 
-int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, int32_t C,
-                               int32_t name, int32_t epoch_size, int32_t skip,
-                               int32_t feature_size, double* out, int mem) {
+// eegfx_extract_features_f64 / _f32: E is the element type of the epochs.  Float epochs take the
+// same routes; the rows are those of the double call on the widened epochs, bit for bit.
+template <typename E>
+int extract_features_api(eegfx_ctx* ctx, const E* epochs, int64_t n, int32_t C, int32_t name,
+                         int32_t epoch_size, int32_t skip, int32_t feature_size, double* out,
+                         int mem) {
   return guarded([&] {
     if (!ctx) fail(EEGFX_EINVAL, "null context");
     check_mem(mem);
@@ -1245,16 +1260,20 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
     if (n == 0) return;
     if (!epochs || !out) fail(EEGFX_EINVAL, "null buffer");
     ctx->activate();
-    const size_t in_bytes = sizeof(double) * (size_t)n * C * EEGFX_POSTSTIMULUS;
+    const size_t in_bytes = sizeof(E) * (size_t)n * C * EEGFX_POSTSTIMULUS;
     const size_t out_bytes = sizeof(double) * (size_t)n * C * feature_size;
     if (mem == EEGFX_MEM_HOST) {
       // Host epochs (the JNI drop-in, IFeatureExtraction.extractFeatures called once per epoch
       // from Spark map closures, LogisticRegressionClassifier.java:55-61, or serial loops,
       // NeuralNetworkClassifier.java:78-86).  Only the window columns [skip, skip+512) of each row
-      // are needed (4,096 of 6,000 bytes).
+      // are needed (4,096 of 6,000 bytes; float epochs: 2,048 of 3,000).  row_w: the packed
+      // window row of the small-batch staging, doubles for both element types (float windows
+      // are widened while they are packed); row_c / row_p: the window and the epoch row as the
+      // caller holds them.
       const size_t row_w = sizeof(double) * EEGFX_DWT8_EPOCH_SIZE;
-      const size_t row_p = sizeof(double) * EEGFX_POSTSTIMULUS;
-      const uint8_t* src = (const uint8_t*)epochs + sizeof(double) * (size_t)skip;
+      const size_t row_c = sizeof(E) * EEGFX_DWT8_EPOCH_SIZE;
+      const size_t row_p = sizeof(E) * EEGFX_POSTSTIMULUS;
+      const uint8_t* src = (const uint8_t*)epochs + sizeof(E) * (size_t)skip;
       if ((size_t)n * C * row_w <= kZeroCopyBytes && features_small_supported(C) &&
           !wide_features(feature_size)) {
         // Small batches (a single epoch above all): latency, not bandwidth.  The window rows are
@@ -1269,8 +1288,15 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
           ctx->mb_stop();
         double* hin = (double*)ctx->pin_in.get((size_t)n * C * row_w);
         double* hout = (double*)ctx->pin_out.get(out_bytes);
-        for (int64_t r = 0; r < n * C; ++r)
-          memcpy((uint8_t*)hin + (size_t)r * row_w, src + (size_t)r * row_p, row_w);
+        for (int64_t r = 0; r < n * C; ++r) {
+          if constexpr (std::is_same<E, float>::value) {
+            const float* w = (const float*)(src + (size_t)r * row_p);
+            double* d = hin + (size_t)r * EEGFX_DWT8_EPOCH_SIZE;
+            for (int k = 0; k < EEGFX_DWT8_EPOCH_SIZE; ++k) d[k] = (double)w[k];
+          } else {
+            memcpy((uint8_t*)hin + (size_t)r * row_w, src + (size_t)r * row_p, row_w);
+          }
+        }
         // The resident server (no launch, no stream sync) takes single epochs: it serves a
         // request's epochs one after another (~7 us each), where a launch runs them on a
         // workgroup each (11 epochs: ~20 us launched against ~80 us served).
@@ -1308,7 +1334,7 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
       // host-link bound; packing the rows with host threads into pinned staging first was slower
       // (2.8e6).
       constexpr int64_t kChunk = 8192;  // epochs per chunk
-      const size_t chunk_bytes = (size_t)std::min<int64_t>(n, kChunk) * C * row_w;
+      const size_t chunk_bytes = (size_t)std::min<int64_t>(n, kChunk) * C * row_c;
       uint8_t* dwin = (uint8_t*)ctx->scratch.get(chunk_bytes);
       double* d_out = (double*)ctx->out.get(out_bytes);
       const bool wide = wide_features(feature_size);
@@ -1316,14 +1342,14 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
       ctx->tic();
       for (int64_t e0 = 0; e0 < n; e0 += kChunk) {
         const int64_t m = std::min<int64_t>(kChunk, n - e0);
-        HIP_CHECK(hipMemcpy2DAsync(dwin, row_w, src + (size_t)e0 * C * row_p, row_p, row_w,
+        HIP_CHECK(hipMemcpy2DAsync(dwin, row_c, src + (size_t)e0 * C * row_p, row_p, row_c,
                                    (size_t)(m * C), hipMemcpyHostToDevice, ctx->stream));
         double* rows = d_out + e0 * C * feature_size;
         if (wide)
-          HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)dwin, m, C, 0,
+          HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const E*)dwin, m, C, 0,
                                                feature_size, rows, EEGFX_DWT8_EPOCH_SIZE));
         else
-          HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)dwin, m, C, 0,
+          HIP_CHECK(launch_features_from_epochs(ctx->stream, (const E*)dwin, m, C, 0,
                                                 feature_size, ctx->numerics != EEGFX_EXACT, rows,
                                                 EEGFX_DWT8_EPOCH_SIZE, g));
       }
@@ -1332,7 +1358,7 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
       ctx->drain();
       return;
     }
-    const double* d_in = (const double*)stage_in(ctx, ctx->scratch, epochs, in_bytes, mem);
+    const E* d_in = (const E*)stage_in(ctx, ctx->scratch, epochs, in_bytes, mem);
     double* d_out = mem == EEGFX_MEM_DEVICE ? out : (double*)ctx->out.get(out_bytes);
     if (wide_features(feature_size)) {
       ctx->tic();
@@ -1352,6 +1378,66 @@ int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, 
       ctx->drain();
     }
   });
+}
+
+// eegfx_process_recording_epochs / _f32 with epochs_out != NULL.
+template <typename E>
+int process_recording_epochs_api(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
+                                 int32_t ct, const int32_t* cols, const float* res, int32_t C,
+                                 const int64_t* pos, int64_t n, double* features, E* epochs_out,
+                                 int mem) {
+  return guarded([&] {
+    if (!ctx) fail(EEGFX_EINVAL, "null context");
+    check_mem(mem);
+    if (fmt != EEGFX_INT_16 && fmt != EEGFX_IEEE_FLOAT_32) fail(EEGFX_EINVAL, "format %d", fmt);
+    if (n_frames < 0 || n < 0 || ct < 1) fail(EEGFX_EINVAL, "negative size");
+    if (n > 0 && (!raw || !pos || !features)) fail(EEGFX_EINVAL, "null buffer");
+    const ChanSel sel = make_sel(cols, res, C, ct);
+    if (mem == EEGFX_MEM_HOST) check_positions(pos, n, n_frames);
+    if (n == 0) return;
+    ctx->activate();
+    const size_t raw_bytes = (size_t)n_frames * ct * (fmt == EEGFX_INT_16 ? 2 : 4);
+    const size_t ep_bytes = sizeof(E) * (size_t)n * C * EEGFX_POSTSTIMULUS;
+    const size_t f_bytes = sizeof(double) * (size_t)n * C * EEGFX_DWT8_FEATURE_SIZE;
+    const void* d_raw = stage_in(ctx, ctx->raw, raw, raw_bytes, mem);
+    const int64_t* d_pos = (const int64_t*)stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
+    E* d_ep = mem == EEGFX_MEM_DEVICE ? epochs_out : (E*)ctx->scratch.get(ep_bytes);
+    double* d_f = mem == EEGFX_MEM_DEVICE ? features : (double*)ctx->out.get(f_bytes);
+    run_epochs_and_features(ctx, d_raw, fmt, n_frames, ct, sel, C, d_pos, n, d_ep, d_f);
+    if (mem == EEGFX_MEM_HOST) {
+      HIP_CHECK(hipMemcpyAsync(epochs_out, d_ep, ep_bytes, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(features, d_f, f_bytes, hipMemcpyDeviceToHost, ctx->stream));
+      ctx->drain();
+    }
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
+                         int32_t ct, const int32_t* cols, const float* res, int32_t C,
+                         const int64_t* pos, int64_t n, double* epochs_out, int mem) {
+  return cut_epochs_api(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, epochs_out, mem);
+}
+
+int eegfx_cut_epochs_f32(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
+                         int32_t ct, const int32_t* cols, const float* res, int32_t C,
+                         const int64_t* pos, int64_t n, float* epochs_out, int mem) {
+  return cut_epochs_api(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, epochs_out, mem);
+}
+
+int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, int32_t C,
+                               int32_t name, int32_t epoch_size, int32_t skip,
+                               int32_t feature_size, double* out, int mem) {
+  return extract_features_api(ctx, epochs, n, C, name, epoch_size, skip, feature_size, out, mem);
+}
+
+int eegfx_extract_features_f32(eegfx_ctx* ctx, const float* epochs, int64_t n, int32_t C,
+                               int32_t name, int32_t epoch_size, int32_t skip,
+                               int32_t feature_size, double* out, int mem) {
+  return extract_features_api(ctx, epochs, n, C, name, epoch_size, skip, feature_size, out, mem);
 }
 
 int eegfx_process_recording(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
@@ -1406,7 +1492,9 @@ int eegfx_process_recording_fe(eegfx_ctx* ctx, const void* raw, int32_t fmt, int
     double* d_out = mem == EEGFX_MEM_DEVICE ? features : (double*)ctx->out.get(out_bytes);
     // The two passes: the epochs into scratch memory, then the rows from them.  (A fused raw ->
     // rows pyramid kernel measured slower than this at feature size 512: DESIGN.md 5.4.1.)
-    double* ep = (double*)ctx->scratch.get(sizeof(double) * (size_t)n * C * EEGFX_POSTSTIMULUS);
+    // The scratch epochs are float32: the fp32 samples as the cut holds them (3,000 C bytes per
+    // epoch), widened again by the kernels that read them -- the rows are those of double scratch.
+    float* ep = (float*)ctx->scratch.get(sizeof(float) * (size_t)n * C * EEGFX_POSTSTIMULUS);
     ctx->tic();
     HIP_CHECK(launch_cut_epochs(ctx->stream, d_raw, fmt, n_frames, ct, sel, C, d_pos, n, ep,
                                 ctx->fused.get(fused_scratch_bytes(n, C)), ctx->err_dev));
@@ -1434,30 +1522,19 @@ int eegfx_process_recording_epochs(eegfx_ctx* ctx, const void* raw, int32_t fmt,
   if (!epochs_out)
     return eegfx_process_recording(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, features,
                                    mem);
-  return guarded([&] {
-    if (!ctx) fail(EEGFX_EINVAL, "null context");
-    check_mem(mem);
-    if (fmt != EEGFX_INT_16 && fmt != EEGFX_IEEE_FLOAT_32) fail(EEGFX_EINVAL, "format %d", fmt);
-    if (n_frames < 0 || n < 0 || ct < 1) fail(EEGFX_EINVAL, "negative size");
-    if (n > 0 && (!raw || !pos || !features)) fail(EEGFX_EINVAL, "null buffer");
-    const ChanSel sel = make_sel(cols, res, C, ct);
-    if (mem == EEGFX_MEM_HOST) check_positions(pos, n, n_frames);
-    if (n == 0) return;
-    ctx->activate();
-    const size_t raw_bytes = (size_t)n_frames * ct * (fmt == EEGFX_INT_16 ? 2 : 4);
-    const size_t ep_bytes = sizeof(double) * (size_t)n * C * EEGFX_POSTSTIMULUS;
-    const size_t f_bytes = sizeof(double) * (size_t)n * C * EEGFX_DWT8_FEATURE_SIZE;
-    const void* d_raw = stage_in(ctx, ctx->raw, raw, raw_bytes, mem);
-    const int64_t* d_pos = (const int64_t*)stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
-    double* d_ep = mem == EEGFX_MEM_DEVICE ? epochs_out : (double*)ctx->scratch.get(ep_bytes);
-    double* d_f = mem == EEGFX_MEM_DEVICE ? features : (double*)ctx->out.get(f_bytes);
-    run_epochs_and_features(ctx, d_raw, fmt, n_frames, ct, sel, C, d_pos, n, d_ep, d_f);
-    if (mem == EEGFX_MEM_HOST) {
-      HIP_CHECK(hipMemcpyAsync(epochs_out, d_ep, ep_bytes, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(hipMemcpyAsync(features, d_f, f_bytes, hipMemcpyDeviceToHost, ctx->stream));
-      ctx->drain();
-    }
-  });
+  return process_recording_epochs_api(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, features,
+                                      epochs_out, mem);
+}
+
+int eegfx_process_recording_epochs_f32(eegfx_ctx* ctx, const void* raw, int32_t fmt,
+                                       int64_t n_frames, int32_t ct, const int32_t* cols,
+                                       const float* res, int32_t C, const int64_t* pos, int64_t n,
+                                       double* features, float* epochs_out, int mem) {
+  if (!epochs_out)
+    return eegfx_process_recording(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, features,
+                                   mem);
+  return process_recording_epochs_api(ctx, raw, fmt, n_frames, ct, cols, res, C, pos, n, features,
+                                      epochs_out, mem);
 }
 
 // Config 5 (BASELINE.json configs[4]): a long recording in host memory, streamed to the device in
@@ -1904,6 +1981,24 @@ int eegfx_odp_get_data(const eegfx_odp* odp, double* out) {
                              sizeof(double) * 3 * EEGFX_POSTSTIMULUS * (size_t)odp->n_epochs,
                              hipMemcpyDeviceToHost, odp->ctx->stream));
     odp->ctx->drain();
+  });
+}
+
+int eegfx_odp_get_data_f32(const eegfx_odp* odp, float* out) {
+  return guarded([&] {
+    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
+    if (!odp->n_epochs) return;
+    if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
+    eegfx_ctx* ctx = odp->ctx;
+    ctx->activate();
+    // the resident epochs stay double; a narrowing kernel feeds the copy (exact: every value is a
+    // widened fp32), so half the bytes cross the host link
+    const int64_t count = 3 * EEGFX_POSTSTIMULUS * (int64_t)odp->n_epochs;
+    float* d_f32 = (float*)ctx->scratch.get(sizeof(float) * (size_t)count);
+    HIP_CHECK(launch_narrow_epochs(ctx->stream, (const double*)odp->d_epochs, d_f32, count));
+    HIP_CHECK(hipMemcpyAsync(out, d_f32, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost,
+                             ctx->stream));
+    ctx->drain();
   });
 }
 

@@ -6,6 +6,9 @@
 //                                (WaveletTransform.java:107-141, SignalProcessing.java:38-52)
 //   fused kernel                 see fused.hip (raw -> features, the benchmarked hot path)
 //   synth_kernel                 deterministic synthetic recordings for tests and bench.py
+//   narrow_epochs_kernel         resident double epochs -> float32 (eegfx_odp_get_data_f32)
+// The epoch writers and readers take the epochs' element type as a template parameter E: double
+// (the reference's double[n][C][750]) or float (the fp32 values it widens, the *_f32 entries).
 //
 // Compiled with -ffp-contract=off: every fp32/fp64 expression is evaluated as written, one
 // correctly rounded IEEE operation at a time, matching the Java (strictfp-equivalent) order.
@@ -22,14 +25,61 @@
 namespace eegfx {
 namespace dev {
 
+// Float32 epochs (eegfx_cut_epochs_f32 and the epochs of eegfx_process_recording_epochs_f32): the
+// kernels below hold every epoch sample as the fp32 value v - base before they widen it, and the
+// float instantiations (E = float) store that value as it is.  A lane's 16-byte store then covers
+// four samples where the double store covers two, so the store loops are rebuilt around quads:
+// the rows a workgroup writes form one run of `count` floats at `o` (row r's sample f at
+// o[r * kPost + f]; value(r, f) gives it), and lane t stores samples [head + 4 t, head + 4 t + 4)
+// of it as one float4, a wave's instruction covering 1 KB as the double2 stores do.  A float* is
+// only 4-byte aligned and an epoch row is 3,000 bytes, so the run starts on any 4-byte boundary:
+// `head` (0..3) floats up to the first 16-byte boundary and the 0..3 floats past the last whole
+// quad are stored one by one, by the first lanes.  A quad may span two rows (750 = 2 mod 4, and
+// an odd head splits even a pair).
+template <int NT, typename V>
+__device__ __forceinline__ void store_f32_run(float* __restrict__ o, int count, int t, V value) {
+  const int head0 = (int)((0u - (uint32_t)((uintptr_t)o >> 2)) & 3u);
+  const int head = head0 < count ? head0 : count;
+  const int nq = (count - head) >> 2;
+  for (int q = t; q < nq; q += NT) {
+    const int i = head + 4 * q;
+    int r = i / kPost, f = i - r * kPost;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = value(r, f);
+      if (++f == kPost) { f = 0; ++r; }
+    }
+    *(float4*)(o + i) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  const int ntail = count - head - 4 * nq;
+  if (t < head + ntail) {
+    const int i = t < head ? t : 4 * nq + t;  // = head + 4 nq + (t - head)
+    const int r = i / kPost;
+    o[i] = value(r, i - r * kPost);
+  }
+}
+
+// The rows of an LDS-staged chunk: frames [0, nf) of each of the C channel rows at `o`.  A whole
+// epoch (nf = 750, the usual case) is one run; a partial chunk is one run of nf floats per row.
+template <typename V>
+__device__ __forceinline__ void store_f32_rows(float* __restrict__ o, int C, int nf, int t, V value) {
+  if (nf == kPost) {
+    store_f32_run<256>(o, C * kPost, t, value);
+  } else {
+    for (int c = 0; c < C; ++c)
+      store_f32_run<256>(o + c * kPost, nf, t, [&](int, int f) { return value(c, f); });
+  }
+}
+
 // a3 + a5..a7.  One workgroup per epoch.  Lanes 0..C-1 fold the 100 pre-stimulus samples of
 // their channel sequentially in fp32 (Baseline.java:29-42 -- order-exact, so no tree reduction),
 // then all lanes write the 750 post-stimulus samples, coalesced.
-template <typename T>
+template <typename T, typename E = double>
 __global__ __launch_bounds__(256) void cut_epochs_kernel(const T* __restrict__ raw, int64_t n_frames,
                                                          int ct, ChanSel sel, int C,
                                                          const int64_t* __restrict__ pos,
-                                                         double* __restrict__ out,
+                                                         E* __restrict__ out,
                                                          int* __restrict__ err) {
   __shared__ float base[kMaxChannels];
   const int64_t e = blockIdx.x;
@@ -55,37 +105,46 @@ __global__ __launch_bounds__(256) void cut_epochs_kernel(const T* __restrict__ r
     base[c] = b / (float)kPre;
   }
   __syncthreads();
-  double* o = out + e * C * kPost;
+  E* o = out + e * C * kPost;
   for (int idx = threadIdx.x; idx < C * kPost; idx += blockDim.x) {
     const int c = idx / kPost;
     const int64_t f = p + (idx - c * kPost);
     const float v = (f >= 0 && f < n_frames) ? (float)raw[f * ct + sel.col[c]] * sel.res[c] : 0.0f;
-    o[idx] = (double)(v - base[c]);
+    o[idx] = (E)(v - base[c]);  // this fallback stores single samples for both element types
   }
 }
 
 // a5..a7 write pass of the materialised epochs (getData()): the per-(epoch, channel) baselines
 // come from the LDS-staged baseline kernels; each lane writes two consecutive samples of one
 // channel row as one 16-byte store (750 is even, so a pair never straddles two rows).
-template <typename T>
+template <typename T, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_kernel(const T* __restrict__ raw, int64_t n_frames,
                                                         int ct, ChanSel sel, int C,
                                                         const int64_t* __restrict__ pos,
                                                         const float* __restrict__ base,
-                                                        double* __restrict__ out) {
+                                                        E* __restrict__ out) {
   const int64_t e = blockIdx.x;
   const int64_t p0 = pos[e];
   const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
-  double* o = out + e * C * kPost;
-  for (int idx = 2 * (int)threadIdx.x; idx < C * kPost; idx += 2 * (int)blockDim.x) {
-    const int c = idx / kPost;
-    const int64_t f = p + (idx - c * kPost);
-    const int col = sel.col[c];
-    const float r = sel.res[c], b = base[e * C + c];
-    // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-    const float v0 = f >= 0 && f < n_frames ? (float)raw[f * ct + col] * r : 0.0f;
-    const float v1 = f + 1 >= 0 && f + 1 < n_frames ? (float)raw[(f + 1) * ct + col] * r : 0.0f;
-    *(double2*)(o + idx) = make_double2((double)(v0 - b), (double)(v1 - b));
+  E* o = out + e * C * kPost;
+  if constexpr (std::is_same<E, float>::value) {
+    store_f32_run<256>(o, C * kPost, (int)threadIdx.x, [&](int c, int fi) {
+      const int64_t f = p + fi;
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v = f >= 0 && f < n_frames ? (float)raw[f * ct + sel.col[c]] * sel.res[c] : 0.0f;
+      return v - base[e * C + c];
+    });
+  } else {
+    for (int idx = 2 * (int)threadIdx.x; idx < C * kPost; idx += 2 * (int)blockDim.x) {
+      const int c = idx / kPost;
+      const int64_t f = p + (idx - c * kPost);
+      const int col = sel.col[c];
+      const float r = sel.res[c], b = base[e * C + c];
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v0 = f >= 0 && f < n_frames ? (float)raw[f * ct + col] * r : 0.0f;
+      const float v1 = f + 1 >= 0 && f + 1 < n_frames ? (float)raw[(f + 1) * ct + col] * r : 0.0f;
+      *(double2*)(o + idx) = make_double2((double)(v0 - b), (double)(v1 - b));
+    }
   }
 }
 
@@ -96,10 +155,10 @@ __global__ __launch_bounds__(256) void cut_write_kernel(const T* __restrict__ ra
 // the LDS-staged passes below (4.6 ms there, profiles/r03az/) it serves only the layouts they skip:
 // a few channels of a wide montage (ct > 8 C) or a raw buffer that is not dword aligned.
 constexpr int kCutPairs = 5;
-template <typename T>
+template <typename T, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_small_kernel(
     const T* __restrict__ raw, int64_t n_frames, int ct, ChanSel sel, int C,
-    const int64_t* __restrict__ pos, const float* __restrict__ base, double* __restrict__ out) {
+    const int64_t* __restrict__ pos, const float* __restrict__ base, E* __restrict__ out) {
   __shared__ int s_col[kMaxChannels];
   __shared__ float s_res[kMaxChannels], s_base[kMaxChannels];
   const int t = threadIdx.x;
@@ -112,29 +171,37 @@ __global__ __launch_bounds__(256) void cut_write_small_kernel(
   const int64_t p0 = pos[e];
   const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
   __syncthreads();
-  double* o = out + e * C * kPost;
-  const int npairs = C * (kPost / 2);  // <= 256 * kCutPairs (launcher)
-  float v0[kCutPairs], v1[kCutPairs];
+  E* o = out + e * C * kPost;
+  if constexpr (std::is_same<E, float>::value) {  // at most 640 quads: three trips
+    store_f32_run<256>(o, C * kPost, t, [&](int c, int fi) {
+      const int64_t f = p + fi;
+      const float v = f >= 0 && f < n_frames ? (float)raw[f * ct + s_col[c]] * s_res[c] : 0.0f;
+      return v - s_base[c];
+    });
+  } else {
+    const int npairs = C * (kPost / 2);  // <= 256 * kCutPairs (launcher)
+    float v0[kCutPairs], v1[kCutPairs];
 #pragma unroll
-  for (int u = 0; u < kCutPairs; ++u) {
-    const int idx = 256 * u + t;
-    v0[u] = v1[u] = 0.0f;
-    if (idx < npairs) {
-      const int c = idx / (kPost / 2);
-      const int64_t f = p + 2 * (idx - c * (kPost / 2));
-      const int col = s_col[c];
-      const float r = s_res[c];
-      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-      if (f >= 0 && f < n_frames) v0[u] = (float)raw[f * ct + col] * r;
-      if (f + 1 >= 0 && f + 1 < n_frames) v1[u] = (float)raw[(f + 1) * ct + col] * r;
+    for (int u = 0; u < kCutPairs; ++u) {
+      const int idx = 256 * u + t;
+      v0[u] = v1[u] = 0.0f;
+      if (idx < npairs) {
+        const int c = idx / (kPost / 2);
+        const int64_t f = p + 2 * (idx - c * (kPost / 2));
+        const int col = s_col[c];
+        const float r = s_res[c];
+        // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+        if (f >= 0 && f < n_frames) v0[u] = (float)raw[f * ct + col] * r;
+        if (f + 1 >= 0 && f + 1 < n_frames) v1[u] = (float)raw[(f + 1) * ct + col] * r;
+      }
     }
-  }
 #pragma unroll
-  for (int u = 0; u < kCutPairs; ++u) {
-    const int idx = 256 * u + t;
-    if (idx < npairs) {
-      const float b = s_base[idx / (kPost / 2)];
-      *(double2*)(o + 2 * idx) = make_double2((double)(v0[u] - b), (double)(v1[u] - b));
+    for (int u = 0; u < kCutPairs; ++u) {
+      const int idx = 256 * u + t;
+      if (idx < npairs) {
+        const float b = s_base[idx / (kPost / 2)];
+        *(double2*)(o + 2 * idx) = make_double2((double)(v0[u] - b), (double)(v1[u] - b));
+      }
     }
   }
 }
@@ -282,11 +349,11 @@ constexpr int kCfEpochs = 8;
 constexpr int kCfDwords = 1127;  // dwords staged per epoch: (2 + 750 * 6 + 3) / 4, rounded up
 constexpr int kCfStride = 1160;  // LDS dwords per epoch: 1,127 + 12 skew dwords, = 8 (mod 32)
 __device__ __forceinline__ int cf_lds_dword(int d) { return d + (int)(((uint32_t)d * 683u) >> 16); }
-template <bool FAST, bool FEAT = true>
+template <bool FAST, bool FEAT = true, typename E = double>
 __global__ __launch_bounds__(256) void cut_features_c3_kernel(
     const int16_t* __restrict__ raw, int64_t n_frames, ChanSel sel,
     const int64_t* __restrict__ pos, const float* __restrict__ base, int64_t n,
-    double* __restrict__ out, double* __restrict__ fout, Guard guard) {
+    E* __restrict__ out, double* __restrict__ fout, Guard guard) {
   constexpr int CT = 3, C = 3, FB = 6, F = 48;
   static_assert(kCfEpochs * F * 8 + 768 * 8 <= kCfEpochs * kCfStride * 4, "rows + scratch alias");
   __shared__ __attribute__((aligned(16))) uint32_t stage[kCfEpochs * kCfStride];
@@ -343,7 +410,16 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
   const int16_t* hs = (const int16_t*)stage;
   // staged half h of epoch m (h counted from the epoch's first staged byte)
   auto half = [&](int m, int h) { return hs[2 * m * kCfStride + h + 2 * (int)(((uint32_t)(h >> 1) * 683u) >> 16)]; };
-  {  // 2. rows: pair q of (epoch m, channel c) = frames 2q, 2q + 1
+  if constexpr (std::is_same<E, float>::value) {
+    // 2. rows, float32: the workgroup's ne epochs are one run of ne * 3 * 750 floats
+    store_f32_run<256>(out + e0 * C * kPost, ne * C * kPost, tid, [&](int rr, int f) {
+      const int m = rr / C, c = rr - m * C;
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v =
+          sP[m] + f < n_frames ? (float)half(m, sH[m] + 3 * f + s_col[c]) * s_res[c] : 0.0f;
+      return v - s_base[m * C + c];
+    });
+  } else {  // 2. rows: pair q of (epoch m, channel c) = frames 2q, 2q + 1
     constexpr int HP = kPost / 2, PER_E = C * HP;
     int idx = tid;
     int m = idx / PER_E, rem = idx - m * PER_E;
@@ -437,10 +513,10 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
 #define EEGFX_CUT_LDS_MAX (64 * 1024)
 #endif
 constexpr int kCutLdsMax = EEGFX_CUT_LDS_MAX;
-template <typename T, bool FEAT = false, bool FAST = false>
+template <typename T, bool FEAT = false, bool FAST = false, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_lds_kernel(
     const T* __restrict__ raw, int64_t n_frames, int ct, ChanSel sel, int C,
-    const int64_t* __restrict__ pos, const float* __restrict__ base, double* __restrict__ out,
+    const int64_t* __restrict__ pos, const float* __restrict__ base, E* __restrict__ out,
     int nfc, double* __restrict__ fout = nullptr, Guard guard = Guard{nullptr, nullptr, nullptr}) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stage[];
   __shared__ int s_col[kMaxChannels];
@@ -481,31 +557,44 @@ __global__ __launch_bounds__(256) void cut_write_lds_kernel(
     }
   }
   __syncthreads();
-  // rows: pair q of channel c covers frames f0 + 2q, f0 + 2q + 1
-  const int hp = nf / 2, npairs = C * hp, sc = 256 / hp, sq = 256 % hp;
-  int c = t / hp, q = t - (t / hp) * hp;
-  double* o = out + e * C * kPost + f0;
-  for (int idx = t; idx < npairs; idx += 256) {
-    const int col = s_col[c];
-    const float r = s_res[c], b = s_base[c];
-    const int f = 2 * q;
-    float s0, s1;
-    if constexpr (sizeof(T) == 2) {
-      const int16_t* h = (const int16_t*)stage;
-      s0 = (float)h[2 * f * FS + col];
-      s1 = (float)h[2 * (f + 1) * FS + col];
-    } else {
-      const float* h = (const float*)stage;
-      s0 = h[f * FS + col];
-      s1 = h[(f + 1) * FS + col];
+  if constexpr (std::is_same<E, float>::value) {
+    float* o = out + e * C * kPost + f0;
+    auto value = [&](int c, int f) {
+      float s0;
+      if constexpr (sizeof(T) == 2) s0 = (float)((const int16_t*)stage)[2 * f * FS + s_col[c]];
+      else s0 = ((const float*)stage)[f * FS + s_col[c]];
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v = g0 + f < n_frames ? s0 * s_res[c] : 0.0f;
+      return v - s_base[c];
+    };
+    store_f32_rows(o, C, nf, t, value);
+  } else {
+    // rows: pair q of channel c covers frames f0 + 2q, f0 + 2q + 1
+    const int hp = nf / 2, npairs = C * hp, sc = 256 / hp, sq = 256 % hp;
+    int c = t / hp, q = t - (t / hp) * hp;
+    double* o = out + e * C * kPost + f0;
+    for (int idx = t; idx < npairs; idx += 256) {
+      const int col = s_col[c];
+      const float r = s_res[c], b = s_base[c];
+      const int f = 2 * q;
+      float s0, s1;
+      if constexpr (sizeof(T) == 2) {
+        const int16_t* h = (const int16_t*)stage;
+        s0 = (float)h[2 * f * FS + col];
+        s1 = (float)h[2 * (f + 1) * FS + col];
+      } else {
+        const float* h = (const float*)stage;
+        s0 = h[f * FS + col];
+        s1 = h[(f + 1) * FS + col];
+      }
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v0 = g0 + f < n_frames ? s0 * r : 0.0f;
+      const float v1 = g0 + f + 1 < n_frames ? s1 * r : 0.0f;
+      *(double2*)(o + (int64_t)c * kPost + f) = make_double2((double)(v0 - b), (double)(v1 - b));
+      c += sc;
+      q += sq;
+      if (q >= hp) { q -= hp; ++c; }
     }
-    // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-    const float v0 = g0 + f < n_frames ? s0 * r : 0.0f;
-    const float v1 = g0 + f + 1 < n_frames ? s1 * r : 0.0f;
-    *(double2*)(o + (int64_t)c * kPost + f) = make_double2((double)(v0 - b), (double)(v1 - b));
-    c += sc;
-    q += sq;
-    if (q >= hp) { q -= hp; ++c; }
   }
   if constexpr (FEAT) {  // one chunk per epoch (launcher): the window frames are staged
     double* gx = (double*)((uint8_t*)stage + staged_features_lds((size_t)nf * FS * 4, C) - 64 * 8 - 16);
@@ -526,10 +615,10 @@ __global__ __launch_bounds__(256) void cut_write_lds_kernel(
 // the dword that holds its first frame, without per-frame padding; lanes reading the sample pairs
 // of one channel are 2 frames apart (3 dwords at 3 channels: an odd stride, no bank conflicts).
 // The dword holding the recording's last two bytes is read as a half so no load passes its end.
-template <bool FEAT = false, bool FAST = false>
+template <bool FEAT = false, bool FAST = false, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_lds_packed_kernel(
     const int16_t* __restrict__ raw, int64_t n_frames, int ct, ChanSel sel, int C,
-    const int64_t* __restrict__ pos, const float* __restrict__ base, double* __restrict__ out,
+    const int64_t* __restrict__ pos, const float* __restrict__ base, E* __restrict__ out,
     int nfc, double* __restrict__ fout = nullptr, Guard guard = Guard{nullptr, nullptr, nullptr}) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stage[];
   __shared__ int s_col[kMaxChannels];
@@ -571,20 +660,28 @@ __global__ __launch_bounds__(256) void cut_write_lds_packed_kernel(
   }
   __syncthreads();
   const int16_t* h = (const int16_t*)((const uint8_t*)stage + delta);
-  const int hp = nf / 2, npairs = C * hp, sc = 256 / hp, sq = 256 % hp;
-  int c = t / hp, q = t - (t / hp) * hp;
-  double* o = out + e * C * kPost + f0;
-  for (int idx = t; idx < npairs; idx += 256) {
-    const int col = s_col[c];
-    const float r = s_res[c], b = s_base[c];
-    const int f = 2 * q;
-    // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-    const float v0 = g0 + f < n_frames ? (float)h[f * ct + col] * r : 0.0f;
-    const float v1 = g0 + f + 1 < n_frames ? (float)h[(f + 1) * ct + col] * r : 0.0f;
-    *(double2*)(o + (int64_t)c * kPost + f) = make_double2((double)(v0 - b), (double)(v1 - b));
-    c += sc;
-    q += sq;
-    if (q >= hp) { q -= hp; ++c; }
+  if constexpr (std::is_same<E, float>::value) {
+    store_f32_rows(out + e * C * kPost + f0, C, nf, t, [&](int c, int f) {
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v = g0 + f < n_frames ? (float)h[f * ct + s_col[c]] * s_res[c] : 0.0f;
+      return v - s_base[c];
+    });
+  } else {
+    const int hp = nf / 2, npairs = C * hp, sc = 256 / hp, sq = 256 % hp;
+    int c = t / hp, q = t - (t / hp) * hp;
+    double* o = out + e * C * kPost + f0;
+    for (int idx = t; idx < npairs; idx += 256) {
+      const int col = s_col[c];
+      const float r = s_res[c], b = s_base[c];
+      const int f = 2 * q;
+      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
+      const float v0 = g0 + f < n_frames ? (float)h[f * ct + col] * r : 0.0f;
+      const float v1 = g0 + f + 1 < n_frames ? (float)h[(f + 1) * ct + col] * r : 0.0f;
+      *(double2*)(o + (int64_t)c * kPost + f) = make_double2((double)(v0 - b), (double)(v1 - b));
+      c += sc;
+      q += sq;
+      if (q >= hp) { q -= hp; ++c; }
+    }
   }
   if constexpr (FEAT) {  // one chunk per epoch (launcher): the window frames are staged
     double* gx = (double*)((uint8_t*)stage + staged_features_lds((size_t)total * 4, C) - 64 * 8 - 16);
@@ -624,12 +721,22 @@ typedef double f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
 // through a 1 KB LDS tile, leave as whole 128-byte runs into `out`, and lanes 0-7 add their
 // squares to the epoch's sum in index order (the reference's sequential sum,
 // SignalProcessing.java:38-52); at the end the wave rescales its rows in place (L2-resident).
-template <bool FAST, bool ROWS_OUT>
-__global__ __launch_bounds__(64) void features_from_epochs_kernel(const double* __restrict__ ep,
+//
+// Float32 epochs (E = float, eegfx_extract_features_f32 and the scratch epochs of
+// eegfx_process_recording_fe): a window is 2 KB, read as 16 loads of four floats per lane (quad
+// q = 64 (j % 2) + lane of window j / 2), again 1 KB of one window per load instruction.  The
+// window starts at ep + 4 (row * row_stride + skip) bytes, on any 4-byte boundary, so the quads
+// are typed 4-byte aligned, as the double pairs are typed 8-byte aligned (an odd skip): the
+// 16-byte global load takes any dword address.  The samples are widened as they are written into
+// the same LDS layout, and everything after that is the double kernel's: the rows are its rows.
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+template <bool FAST, bool ROWS_OUT, typename E = double>
+__global__ __launch_bounds__(64) void features_from_epochs_kernel(const E* __restrict__ ep,
                                                                   int64_t n, int C, int skip,
                                                                   int nfeat, int row_stride,
                                                                   double* __restrict__ out,
                                                                   Guard guard) {
+  constexpr bool F32 = std::is_same<E, float>::value;
   __shared__ __attribute__((aligned(16))) double win[8 * kFeWin];
   extern __shared__ __attribute__((aligned(16))) double fsmem[];
   const int lane = threadIdx.x;
@@ -643,14 +750,24 @@ __global__ __launch_bounds__(64) void features_from_epochs_kernel(const double* 
   // quad q = 64 (j % 4) + lane of window j / 4: doubles 2q, 2q + 1 of segment q / 32.  Epochs
   // past n read the last epoch's window (the loads stay unconditional; the result is dropped).
   // Channel c + 1's windows are in flight while channel c runs the filter bank.
-  f64x2_a8 v[32];
+  constexpr int NV = F32 ? 16 : 32;
+  typename std::conditional<F32, f32x4_a4, f64x2_a8>::type v[NV];
   auto load = [&](int c) {
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const int g = j >> 2;
-      const int64_t e = e0 + (g < ne ? g : ne - 1);
-      const int q = ((j & 3) << 6) | lane;
-      v[j] = __builtin_nontemporal_load((const f64x2_a8*)(ep + (e * C + c) * row_stride + skip + 2 * q));
+    for (int j = 0; j < NV; ++j) {
+      if constexpr (F32) {
+        const int g = j >> 1;
+        const int64_t e = e0 + (g < ne ? g : ne - 1);
+        const int q = ((j & 1) << 6) | lane;
+        v[j] = __builtin_nontemporal_load(
+            (const f32x4_a4*)(ep + (e * C + c) * row_stride + skip + 4 * q));
+      } else {
+        const int g = j >> 2;
+        const int64_t e = e0 + (g < ne ? g : ne - 1);
+        const int q = ((j & 3) << 6) | lane;
+        v[j] = __builtin_nontemporal_load(
+            (const f64x2_a8*)(ep + (e * C + c) * row_stride + skip + 2 * q));
+      }
     }
   };
   load(0);
@@ -659,11 +776,20 @@ __global__ __launch_bounds__(64) void features_from_epochs_kernel(const double* 
   for (int c = 0; c < C; ++c) {
     wave_sync();  // the previous channel's LDS reads precede these writes
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const int q = ((j & 3) << 6) | lane;
-      double* d = win + (j >> 2) * kFeWin + (q >> 5) * kFeSeg + 2 * (q & 31);
-      d[0] = v[j].x;
-      d[1] = v[j].y;
+    for (int j = 0; j < NV; ++j) {
+      if constexpr (F32) {  // floats 4q .. 4q + 3 of segment q / 16, widened
+        const int q = ((j & 1) << 6) | lane;
+        double* d = win + (j >> 1) * kFeWin + (q >> 4) * kFeSeg + 4 * (q & 15);
+        d[0] = (double)v[j].x;
+        d[1] = (double)v[j].y;
+        d[2] = (double)v[j].z;
+        d[3] = (double)v[j].w;
+      } else {
+        const int q = ((j & 3) << 6) | lane;
+        double* d = win + (j >> 2) * kFeWin + (q >> 5) * kFeSeg + 2 * (q & 31);
+        d[0] = v[j].x;
+        d[1] = v[j].y;
+      }
     }
     wave_sync();
     if (c + 1 < C) load(c + 1);
@@ -731,11 +857,12 @@ __global__ __launch_bounds__(64) void features_from_epochs_kernel(const double* 
       }
       do {
         const int e = __ffsll((unsigned long long)flagged) - 1;
-        const double* row = ep + (e0 + e) * C * (int64_t)row_stride + skip;
+        const E* row = ep + (e0 + e) * C * (int64_t)row_stride + skip;
         static_assert(768 + kMaxChannels * 16 <= 8 * kFeWin, "the recomputed row fits the windows");
         double* dst = ROWS_OUT ? win + 768 : feat + e * F;  // past the 768-double scratch
-        dwt8_exact_row_wave([&](int c, int k) { return row[(int64_t)c * row_stride + k]; }, C,
-                            nfeat, win, dst, lane);
+        dwt8_exact_row_wave(
+            [&](int c, int k) { return (double)row[(int64_t)c * row_stride + k]; }, C, nfeat, win,
+            dst, lane);
         if constexpr (ROWS_OUT) {
           wave_sync();
           for (int i = lane; i < F; i += 64) o[(int64_t)e * F + i] = dst[i];
@@ -967,14 +1094,18 @@ static int cut_chunk_frames(int frame_bytes, int slack) {
     if ((int64_t)nfc * frame_bytes + slack <= dev::kCutLdsMax || nfc <= 2) return nfc;
   }
 }
-hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
-                             const ChanSel& sel, int C, const int64_t* pos, int64_t n,
-                             double* out, void* scratch, int* err) {
+// E: the epochs' element type (double: eegfx_cut_epochs_f64; float: eegfx_cut_epochs_f32, the
+// same kernels storing the fp32 sample unwidened).
+template <typename E>
+static hipError_t cut_epochs_impl(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                                  const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                                  E* out, void* scratch, int* err) {
   if (n == 0) return hipSuccess;
   dim3 grid((unsigned)n), block(256);
   // baselines by the staged kernels when a layout fits them, then the coalesced write pass
   hipError_t be = hipErrorNotSupported;
-  const bool aligned = ((uintptr_t)out & 15) == 0;  // the write pass stores 16-byte pairs
+  // the write pass stores 16-byte pairs of doubles; its float stores align themselves
+  const bool aligned = std::is_same<E, float>::value || ((uintptr_t)out & 15) == 0;
   if (!aligned) scratch = nullptr;
   if (scratch && fmt == 0 && ct == 3 && C == 3)
     be = launch_fused_baseline(st, raw, n_frames, ct, sel, C, pos, n, scratch, err, nullptr);
@@ -984,7 +1115,7 @@ hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n
     // the reference's 3-channel file: the eight-epoch staged kernel without its feature phase
     // (4.8 -> 4.4 ms per 1M epochs against the per-epoch staged kernel, profiles/r04g)
     const dim3 g8((unsigned)((n + dev::kCfEpochs - 1) / dev::kCfEpochs));
-    hipLaunchKernelGGL((dev::cut_features_c3_kernel<false, false>), g8, block, 0, st,
+    hipLaunchKernelGGL((dev::cut_features_c3_kernel<false, false, E>), g8, block, 0, st,
                        (const int16_t*)raw, n_frames, sel, pos, (const float*)scratch, n, out,
                        nullptr, Guard{nullptr, nullptr, nullptr});
     return hipGetLastError();
@@ -999,9 +1130,9 @@ hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n
       const int nfc = cut_chunk_frames(fbytes, 8);
       const int nchunks = (dev::kPost + nfc - 1) / nfc;
       dim3 g2((unsigned)n, (unsigned)nchunks);
-      hipLaunchKernelGGL(dev::cut_write_lds_packed_kernel<>, g2, block, (size_t)nfc * fbytes + 8, st,
-                         (const int16_t*)raw, n_frames, ct, sel, C, pos, (const float*)scratch,
-                         out, nfc);
+      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<false, false, E>), g2, block,
+                         (size_t)nfc * fbytes + 8, st, (const int16_t*)raw, n_frames, ct, sel, C,
+                         pos, (const float*)scratch, out, nfc);
     } else if (stage && fbytes % 4 == 0) {
       // wide layouts: LDS-staged chunks of the epoch, an even number of frames each
       const int fs_bytes = (fbytes / 4 + 1) * 4;
@@ -1010,39 +1141,52 @@ hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n
       dim3 g2((unsigned)n, (unsigned)nchunks);
       const size_t lds = (size_t)nfc * fs_bytes;
       if (fmt == 0)
-        hipLaunchKernelGGL(dev::cut_write_lds_kernel<int16_t>, g2, block, lds, st,
-                           (const int16_t*)raw, n_frames, ct, sel, C, pos, (const float*)scratch,
-                           out, nfc);
+        hipLaunchKernelGGL((dev::cut_write_lds_kernel<int16_t, false, false, E>), g2, block, lds,
+                           st, (const int16_t*)raw, n_frames, ct, sel, C, pos,
+                           (const float*)scratch, out, nfc);
       else
-        hipLaunchKernelGGL(dev::cut_write_lds_kernel<float>, g2, block, lds, st, (const float*)raw,
-                           n_frames, ct, sel, C, pos, (const float*)scratch, out, nfc);
+        hipLaunchKernelGGL((dev::cut_write_lds_kernel<float, false, false, E>), g2, block, lds,
+                           st, (const float*)raw, n_frames, ct, sel, C, pos,
+                           (const float*)scratch, out, nfc);
     } else if (fmt == 0 && small)
-      hipLaunchKernelGGL(dev::cut_write_small_kernel<int16_t>, grid, block, 0, st,
+      hipLaunchKernelGGL((dev::cut_write_small_kernel<int16_t, E>), grid, block, 0, st,
                          (const int16_t*)raw, n_frames, ct, sel, C, pos, (const float*)scratch, out);
     else if (fmt == 0)
-      hipLaunchKernelGGL(dev::cut_write_kernel<int16_t>, grid, block, 0, st, (const int16_t*)raw,
-                         n_frames, ct, sel, C, pos, (const float*)scratch, out);
+      hipLaunchKernelGGL((dev::cut_write_kernel<int16_t, E>), grid, block, 0, st,
+                         (const int16_t*)raw, n_frames, ct, sel, C, pos, (const float*)scratch, out);
     else if (small)
-      hipLaunchKernelGGL(dev::cut_write_small_kernel<float>, grid, block, 0, st,
+      hipLaunchKernelGGL((dev::cut_write_small_kernel<float, E>), grid, block, 0, st,
                          (const float*)raw, n_frames, ct, sel, C, pos, (const float*)scratch, out);
     else
-      hipLaunchKernelGGL(dev::cut_write_kernel<float>, grid, block, 0, st, (const float*)raw,
+      hipLaunchKernelGGL((dev::cut_write_kernel<float, E>), grid, block, 0, st, (const float*)raw,
                          n_frames, ct, sel, C, pos, (const float*)scratch, out);
     return hipGetLastError();
   }
   if (fmt == 0)
-    hipLaunchKernelGGL(dev::cut_epochs_kernel<int16_t>, grid, block, 0, st,
+    hipLaunchKernelGGL((dev::cut_epochs_kernel<int16_t, E>), grid, block, 0, st,
                        (const int16_t*)raw, n_frames, ct, sel, C, pos, out, err);
   else
-    hipLaunchKernelGGL(dev::cut_epochs_kernel<float>, grid, block, 0, st, (const float*)raw,
+    hipLaunchKernelGGL((dev::cut_epochs_kernel<float, E>), grid, block, 0, st, (const float*)raw,
                        n_frames, ct, sel, C, pos, out, err);
   return hipGetLastError();
 }
 
-hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
-                               const ChanSel& sel, int C, const int64_t* pos, int64_t n,
-                               double* out, double* feat, bool fast, void* scratch, int* err,
-                               const Guard& guard) {
+hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                             const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                             double* out, void* scratch, int* err) {
+  return cut_epochs_impl(st, raw, fmt, n_frames, ct, sel, C, pos, n, out, scratch, err);
+}
+hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                             const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                             float* out, void* scratch, int* err) {
+  return cut_epochs_impl(st, raw, fmt, n_frames, ct, sel, C, pos, n, out, scratch, err);
+}
+
+template <typename E>
+static hipError_t cut_features_impl(hipStream_t st, const void* raw, int fmt, int64_t n_frames,
+                                    int ct, const ChanSel& sel, int C, const int64_t* pos,
+                                    int64_t n, E* out, double* feat, bool fast, void* scratch,
+                                    int* err, const Guard& guard) {
   if (!cut_features_supported(fmt, ct, C, raw, out, feat)) return hipErrorNotSupported;
   if (n == 0) return hipSuccess;
   hipError_t be = fmt == 0 && ct == 3 && C == 3
@@ -1058,24 +1202,24 @@ hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t
   if (fmt == 0 && ct == 3 && C == 3) {  // the reference's file: eight epochs per workgroup
     const dim3 g8((unsigned)((n + dev::kCfEpochs - 1) / dev::kCfEpochs));
     if (fast)
-      hipLaunchKernelGGL(dev::cut_features_c3_kernel<true>, g8, block, 0, st, (const int16_t*)raw,
-                         n_frames, sel, pos, bs, n, out, feat, g);
+      hipLaunchKernelGGL((dev::cut_features_c3_kernel<true, true, E>), g8, block, 0, st,
+                         (const int16_t*)raw, n_frames, sel, pos, bs, n, out, feat, g);
     else
-      hipLaunchKernelGGL(dev::cut_features_c3_kernel<false>, g8, block, 0, st, (const int16_t*)raw,
-                         n_frames, sel, pos, bs, n, out, feat, g);
+      hipLaunchKernelGGL((dev::cut_features_c3_kernel<false, true, E>), g8, block, 0, st,
+                         (const int16_t*)raw, n_frames, sel, pos, bs, n, out, feat, g);
   } else if (fbytes % 4 != 0) {  // int16, packed frames
     const size_t lds = dev::staged_features_lds((size_t)dev::kPost * fbytes + 8, C);
     if (fast)
-      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, true>), grid, block, lds, st,
+      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, true, E>), grid, block, lds, st,
                          (const int16_t*)raw, n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g);
     else
-      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, false>), grid, block, lds, st,
+      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, false, E>), grid, block, lds, st,
                          (const int16_t*)raw, n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g);
   } else {
     const int fs_bytes = (fbytes / 4 + 1) * 4;
     const size_t lds = dev::staged_features_lds((size_t)dev::kPost * fs_bytes, C);
 #define EEGFX_CF(T, FA)                                                                           \
-    hipLaunchKernelGGL((dev::cut_write_lds_kernel<T, true, FA>), grid, block, lds, st, (const T*)raw, \
+    hipLaunchKernelGGL((dev::cut_write_lds_kernel<T, true, FA, E>), grid, block, lds, st, (const T*)raw, \
                        n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g)
     if (fmt == 0) { if (fast) EEGFX_CF(int16_t, true); else EEGFX_CF(int16_t, false); }
     else { if (fast) EEGFX_CF(float, true); else EEGFX_CF(float, false); }
@@ -1083,13 +1227,29 @@ hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t
   }
   return hipGetLastError();
 }
+hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                               const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                               double* out, double* feat, bool fast, void* scratch, int* err,
+                               const Guard& guard) {
+  return cut_features_impl(st, raw, fmt, n_frames, ct, sel, C, pos, n, out, feat, fast, scratch, err,
+                           guard);
+}
+hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                               const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                               float* out, double* feat, bool fast, void* scratch, int* err,
+                               const Guard& guard) {
+  return cut_features_impl(st, raw, fmt, n_frames, ct, sel, C, pos, n, out, feat, fast, scratch, err,
+                           guard);
+}
 
 // The one-pass kernels stage the whole post-stimulus span of an epoch (one chunk) plus the
 // feature row and scratch in at most 64 KB of LDS: int16 files up to ~40 channels, float32 ~20.
-bool cut_features_supported(int fmt, int ct, int C, const void* raw, const double* out,
-                            const double* feat) {
+// out_align: the alignment the epoch stores need (16: pairs of doubles; 4: the float stores align
+// themselves, store_f32_run).
+static bool cut_features_fit(int fmt, int ct, int C, const void* raw, const void* out,
+                             uintptr_t out_align, const double* feat) {
   if (!(fmt == 0 || fmt == 1) || C < 1 || C > kMaxChannels || ct < 1) return false;
-  if (((uintptr_t)raw & 3) || ((uintptr_t)out & 15) || !feat) return false;
+  if (((uintptr_t)raw & 3) || ((uintptr_t)out & (out_align - 1)) || !feat) return false;
   // the 3-channel kernel stores its rows as 16-byte pairs (normalise_store); the staged kernels
   // store doubles
   if (fmt == 0 && ct == 3 && C == 3 && ((uintptr_t)feat & 15)) return false;
@@ -1100,10 +1260,19 @@ bool cut_features_supported(int fmt, int ct, int C, const void* raw, const doubl
   if (!(fmt == 0 && ct == 3 && C == 3) && !baseline_any_supported(fmt, ct, C)) return false;
   return dev::staged_features_lds(stage, C) <= 64 * 1024;
 }
+bool cut_features_supported(int fmt, int ct, int C, const void* raw, const double* out,
+                            const double* feat) {
+  return cut_features_fit(fmt, ct, C, raw, out, 16, feat);
+}
+bool cut_features_supported(int fmt, int ct, int C, const void* raw, const float* out,
+                            const double* feat) {
+  return cut_features_fit(fmt, ct, C, raw, out, 4, feat);
+}
 
-hipError_t launch_features_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
-                                       int nfeat, bool fast, double* out, int row_stride,
-                                       const Guard& guard) {
+template <typename E>
+static hipError_t features_from_epochs_impl(hipStream_t st, const E* ep, int64_t n, int C, int skip,
+                                            int nfeat, bool fast, double* out, int row_stride,
+                                            const Guard& guard) {
   if (n == 0) return hipSuccess;
   // The rows stay in LDS while the workgroup (33 KB of windows + 8 rows) still fits three times
   // per CU (C <= 20 at 16 features); wider rows go through `out`, which keeps four per CU.
@@ -1115,11 +1284,46 @@ hipError_t launch_features_from_epochs(hipStream_t st, const double* ep, int64_t
   dim3 grid((unsigned)((n + 7) / 8)), block(64);
   const Guard none{nullptr, nullptr, nullptr};
 #define EEGFX_FFE(FA, RO)                                                                         \
-  hipLaunchKernelGGL((dev::features_from_epochs_kernel<FA, RO>), grid, block, smem, st, ep, n, C,  \
-                     skip, nfeat, row_stride, out, FA ? guard : none)
+  hipLaunchKernelGGL((dev::features_from_epochs_kernel<FA, RO, E>), grid, block, smem, st, ep, n, \
+                     C, skip, nfeat, row_stride, out, FA ? guard : none)
   if (fast) { if (rows_out) EEGFX_FFE(true, true); else EEGFX_FFE(true, false); }
   else { if (rows_out) EEGFX_FFE(false, true); else EEGFX_FFE(false, false); }
 #undef EEGFX_FFE
+  return hipGetLastError();
+}
+hipError_t launch_features_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
+                                       int nfeat, bool fast, double* out, int row_stride,
+                                       const Guard& guard) {
+  return features_from_epochs_impl(st, ep, n, C, skip, nfeat, fast, out, row_stride, guard);
+}
+hipError_t launch_features_from_epochs(hipStream_t st, const float* ep, int64_t n, int C, int skip,
+                                       int nfeat, bool fast, double* out, int row_stride,
+                                       const Guard& guard) {
+  return features_from_epochs_impl(st, ep, n, C, skip, nfeat, fast, out, row_stride, guard);
+}
+
+// getData() as float32 (eegfx_odp_get_data_f32): the provider's resident double epochs are
+// widened fp32 values, so the narrowing is exact.  Both buffers are device allocations (16-byte
+// aligned): four doubles in, one 16-byte store out per lane; the last count % 4 by single lanes.
+namespace dev {
+__global__ __launch_bounds__(256) void narrow_epochs_kernel(const double* __restrict__ in,
+                                                            float* __restrict__ out, int64_t count) {
+  const int64_t nq = count >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+    const double2 a = *(const double2*)(in + 4 * q), b = *(const double2*)(in + 4 * q + 2);
+    *(float4*)(out + 4 * q) = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+  }
+  const int64_t t = 4 * nq + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < count) out[t] = (float)in[t];
+}
+}  // namespace dev
+hipError_t launch_narrow_epochs(hipStream_t st, const double* in, float* out, int64_t count) {
+  if (count == 0) return hipSuccess;
+  if (((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+  int64_t blocks = ((count >> 2) + 255) / 256;
+  blocks = blocks < 1 ? 1 : blocks > 65536 ? 65536 : blocks;
+  hipLaunchKernelGGL(dev::narrow_epochs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out,
+                     count);
   return hipGetLastError();
 }
 

@@ -25,6 +25,11 @@ struct ChanSel {
 hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
                              const ChanSel& sel, int C, const int64_t* pos, int64_t n,
                              double* out, void* scratch, int* err);
+// The same epochs as float[n][C][750] (eegfx_cut_epochs_f32): the fp32 value the double form
+// widens, stored as it is; `out` may sit on any 4-byte boundary.
+hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                             const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                             float* out, void* scratch, int* err);
 // The one-pass getData + features (kernels.hip staged_features): baselines, then one workgroup
 // per epoch writes the epoch's rows to `out` (double[n][C][750]) and its normalised dwt-8 row to
 // `feat` (double[n][16 C]) from the same LDS-staged frames.  hipErrorNotSupported when the layout
@@ -35,13 +40,27 @@ hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t
                                const ChanSel& sel, int C, const int64_t* pos, int64_t n,
                                double* out, double* feat, bool fast, void* scratch, int* err,
                                const Guard& guard);
-// row_stride: doubles between consecutive (epoch, channel) rows of `ep` (750 for materialised
+// float epochs (eegfx_process_recording_epochs_f32): the same kernels, the same rows in `feat`
+bool cut_features_supported(int fmt, int ct, int C, const void* raw, const float* out,
+                            const double* feat);
+hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
+                               const ChanSel& sel, int C, const int64_t* pos, int64_t n,
+                               float* out, double* feat, bool fast, void* scratch, int* err,
+                               const Guard& guard);
+// row_stride: elements between consecutive (epoch, channel) rows of `ep` (750 for materialised
 // epochs, 512 for the window-only rows the host path stages)
 // guard (fma numerics): the conditioning guard (guard.h); flagged rows are recomputed under EXACT
 // inside the kernel and counted in guard.total.
 hipError_t launch_features_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
                                        int nfeat, bool fast, double* out, int row_stride,
                                        const Guard& guard);
+// float epochs (eegfx_extract_features_f32; any 4-byte-aligned `ep`): widened as the windows are
+// staged, the rows are those of the double form on the widened epochs
+hipError_t launch_features_from_epochs(hipStream_t st, const float* ep, int64_t n, int C, int skip,
+                                       int nfeat, bool fast, double* out, int row_stride,
+                                       const Guard& guard);
+// double[count] -> float[count] on the device (eegfx_odp_get_data_f32); 16-byte-aligned buffers
+hipError_t launch_narrow_epochs(hipStream_t st, const double* in, float* out, int64_t count);
 // Small host batches (kernels.hip features_small_kernel): rows = n x C x 512 packed window rows,
 // one workgroup per epoch, C <= 16; rows / out may be device pointers of mapped pinned memory.
 bool features_small_supported(int C);
@@ -113,6 +132,8 @@ hipError_t launch_window_wide(hipStream_t st, const void* raw, int fmt, int64_t 
 // The full pyramid (pyramid.hip): feature sizes 17..512, EXACT under both numerics settings, no
 // guard.  ep / row_stride / skip as launch_features_from_epochs; out = double[n][C * nfeat].
 hipError_t launch_pyramid_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
+                                      int nfeat, double* out, int row_stride);
+hipError_t launch_pyramid_from_epochs(hipStream_t st, const float* ep, int64_t n, int C, int skip,
                                       int nfeat, double* out, int row_stride);
 
 // guard.hip: the EXACT recomputation of the rows the generic any-layout kernels flagged (no-op

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "dwt8.h"
 #include "launch.h"
@@ -96,15 +97,20 @@ __device__ __forceinline__ void pyramid_rescale(double* __restrict__ o, int ne, 
 constexpr int kPySeg = kSegLen + 1;
 constexpr int kPyWin = 8 * kPySeg;
 typedef double py_f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
+typedef float py_f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
-// ep: (epoch, channel) rows of row_stride doubles, the window at [skip, skip + 512) of each.
+// ep: (epoch, channel) rows of row_stride elements, the window at [skip, skip + 512) of each.
 // The lane takes its 72 samples to registers, after which the window LDS is free and serves as
 // the tile; the next pass's rows are in flight meanwhile.
-template <int DMIN>
-__global__ __launch_bounds__(64) void pyramid_from_epochs_kernel(const double* __restrict__ ep,
+// E = float (eegfx_extract_features_f32, the scratch epochs of eegfx_process_recording_fe): 16
+// loads of four floats per lane, typed 4-byte aligned (the window starts on any 4-byte boundary),
+// widened as they are written into the same window layout; the pyramid and the tile are unchanged.
+template <int DMIN, typename E = double>
+__global__ __launch_bounds__(64) void pyramid_from_epochs_kernel(const E* __restrict__ ep,
                                                                  int64_t n, int C, int skip, int nf,
                                                                  int row_stride,
                                                                  double* __restrict__ out) {
+  constexpr bool F32 = std::is_same<E, float>::value;
   static_assert(kPyTileMax >= 8 * kPyWin, "the tile covers the windows it replaces");
   __shared__ __attribute__((aligned(16))) double lds[kPyTileMax];
   const int lane = threadIdx.x;
@@ -113,18 +119,26 @@ __global__ __launch_bounds__(64) void pyramid_from_epochs_kernel(const double* _
   const int64_t e0 = (int64_t)blockIdx.x * 8;
   const int ne = (n - e0) < 8 ? (int)(n - e0) : 8;
   const int nsig = ne * C;
-  const double* rows = ep + e0 * C * (int64_t)row_stride + skip;
+  const E* rows = ep + e0 * C * (int64_t)row_stride + skip;
   double* o = out + e0 * F;
   // quad q = 64 (j % 4) + lane of slot j / 4: doubles 2q, 2q + 1 of its window.  Slots past the
   // last signal read the last signal's window (the loads stay unconditional, the result unused).
-  py_f64x2_a8 v[32];
+  constexpr int NV = F32 ? 16 : 32;
+  typename std::conditional<F32, py_f32x4_a4, py_f64x2_a8>::type v[NV];
   auto load = [&](int sig0) {
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const int sg = min(sig0 + (j >> 2), nsig - 1);
-      const int q = ((j & 3) << 6) | lane;
-      v[j] = __builtin_nontemporal_load(
-          (const py_f64x2_a8*)(rows + (int64_t)sg * row_stride + 2 * q));
+    for (int j = 0; j < NV; ++j) {
+      if constexpr (F32) {  // quad q = 64 (j % 2) + lane of slot j / 2: floats 4q .. 4q + 3
+        const int sg = min(sig0 + (j >> 1), nsig - 1);
+        const int q = ((j & 1) << 6) | lane;
+        v[j] = __builtin_nontemporal_load(
+            (const py_f32x4_a4*)(rows + (int64_t)sg * row_stride + 4 * q));
+      } else {
+        const int sg = min(sig0 + (j >> 2), nsig - 1);
+        const int q = ((j & 3) << 6) | lane;
+        v[j] = __builtin_nontemporal_load(
+            (const py_f64x2_a8*)(rows + (int64_t)sg * row_stride + 2 * q));
+      }
     }
   };
   load(0);
@@ -132,11 +146,20 @@ __global__ __launch_bounds__(64) void pyramid_from_epochs_kernel(const double* _
   for (int sig0 = 0; sig0 < nsig; sig0 += 8) {
     wave_sync();  // the previous pass's tile reads precede these writes
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const int q = ((j & 3) << 6) | lane;
-      double* d = lds + (j >> 2) * kPyWin + (q >> 5) * kPySeg + 2 * (q & 31);
-      d[0] = v[j].x;
-      d[1] = v[j].y;
+    for (int j = 0; j < NV; ++j) {
+      if constexpr (F32) {
+        const int q = ((j & 1) << 6) | lane;
+        double* d = lds + (j >> 1) * kPyWin + (q >> 4) * kPySeg + 4 * (q & 15);
+        d[0] = (double)v[j].x;
+        d[1] = (double)v[j].y;
+        d[2] = (double)v[j].z;
+        d[3] = (double)v[j].w;
+      } else {
+        const int q = ((j & 3) << 6) | lane;
+        double* d = lds + (j >> 2) * kPyWin + (q >> 5) * kPySeg + 2 * (q & 31);
+        d[0] = v[j].x;
+        d[1] = v[j].y;
+      }
     }
     wave_sync();
     if (sig0 + 8 < nsig) load(sig0 + 8);
@@ -163,15 +186,16 @@ __global__ __launch_bounds__(64) void pyramid_from_epochs_kernel(const double* _
 
 }  // namespace dev
 
-hipError_t launch_pyramid_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
-                                      int nfeat, double* out, int row_stride) {
+template <typename E>
+static hipError_t pyramid_from_epochs_impl(hipStream_t st, const E* ep, int64_t n, int C, int skip,
+                                           int nfeat, double* out, int row_stride) {
   if (n == 0) return hipSuccess;
   if (nfeat <= 16 || nfeat > dev::kPyMaxFeat || C < 1 || C > kMaxChannels)
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)((n + 7) / 8)), block(64);
 #define EEGFX_PYE(D)                                                                             \
-  hipLaunchKernelGGL((dev::pyramid_from_epochs_kernel<D>), grid, block, 0, st, ep, n, C, skip, \
-                     nfeat, row_stride, out)
+  hipLaunchKernelGGL((dev::pyramid_from_epochs_kernel<D, E>), grid, block, 0, st, ep, n, C,     \
+                     skip, nfeat, row_stride, out)
   switch (dev::pyramid_dmin(nfeat)) {
     case 1: EEGFX_PYE(1); break;
     case 2: EEGFX_PYE(2); break;
@@ -181,6 +205,14 @@ hipError_t launch_pyramid_from_epochs(hipStream_t st, const double* ep, int64_t 
   }
 #undef EEGFX_PYE
   return hipGetLastError();
+}
+hipError_t launch_pyramid_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
+                                      int nfeat, double* out, int row_stride) {
+  return pyramid_from_epochs_impl(st, ep, n, C, skip, nfeat, out, row_stride);
+}
+hipError_t launch_pyramid_from_epochs(hipStream_t st, const float* ep, int64_t n, int C, int skip,
+                                      int nfeat, double* out, int row_stride) {
+  return pyramid_from_epochs_impl(st, ep, n, C, skip, nfeat, out, row_stride);
 }
 
 }  // namespace eegfx

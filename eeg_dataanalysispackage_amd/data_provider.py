@@ -47,12 +47,18 @@ class OffLineDataProvider:
     def num_epochs(self) -> int:
         return int(lib().eegfx_odp_num_epochs(self._h))
 
-    def getData(self) -> np.ndarray:
-        """Epochs as double[n][3][750] (Fz, Cz, Pz)."""
+    def getData(self, dtype=np.float64) -> np.ndarray:
+        """Epochs as double[n][3][750] (Fz, Cz, Pz).  dtype=np.float32: the same values as
+        float[n][3][750] (eegfx_odp_get_data_f32 -- every epoch sample is a widened fp32, so
+        nothing is lost and half the bytes cross the host link)."""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError(f"epochs are float64 or float32, got {dtype}")
         n = self.num_epochs()
-        out = np.empty((n, 3, _lib.POSTSTIMULUS), dtype=np.float64)
+        out = np.empty((n, 3, _lib.POSTSTIMULUS), dtype=dtype)
         if n:
-            check(lib().eegfx_odp_get_data(self._h, ctypes.c_void_p(out.ctypes.data)))
+            fn = lib().eegfx_odp_get_data if dtype == np.float64 else lib().eegfx_odp_get_data_f32
+            check(fn(self._h, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def getDataLabels(self) -> List[float]:

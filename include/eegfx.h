@@ -43,6 +43,9 @@
  * a row comes out as the reference computes it (a NaN or Inf in the window or the baseline gives
  * an all-NaN row, an overflowing sum of squares 0.0 for every finite feature) under both
  * numerics; the rows of the other epochs are unaffected.
+ * Epochs: double[n][C][750] is the reference's interface; every epoch sample is an fp32 value
+ * widened (EpochHolder.java:75-91), and the *_f32 entries carry the same values as float[n][C][750]
+ * at half the bytes (each names the f64 entry it mirrors).
  * Small host batches of eegfx_extract_features_f64 (the per-epoch drop-in) are computed under
  * EXACT in both settings (latency-bound; the guard's counters do not count them), and so are
  * feature sizes above 16 on every path (the full pyramid; see eegfx_extract_features_f64).
@@ -232,6 +235,15 @@ int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n
                          int32_t n_channels_total, const int32_t* cols, const float* res,
                          int32_t C, const int64_t* pos, int64_t n_epochs, double* epochs_out,
                          int mem);
+/* eegfx_cut_epochs_f64 with float32 epochs, float[n][C][750]: element for element the fp32 value
+ * (EpochHolder.setFZ/CZ/PZ stores (double) e[i+100] of a float array) that the f64 entry widens,
+ * stored as it is -- widening this buffer gives the f64 entry's buffer bit for bit (-0.0,
+ * subnormals, +-Inf, NaN included) at half the bytes.  Same layouts, position checks and status
+ * codes.  epochs_out may sit on any 4-byte boundary. */
+int eegfx_cut_epochs_f32(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n_frames,
+                         int32_t n_channels_total, const int32_t* cols, const float* res,
+                         int32_t C, const int64_t* pos, int64_t n_epochs, float* epochs_out,
+                         int mem);
 
 /* IFeatureExtraction.extractFeatures (IFeatureExtraction.java:27-35), batched over n epochs:
  * WaveletTransform(name, epoch_size, skip, feature_size).extractFeatures for each
@@ -249,6 +261,14 @@ int eegfx_cut_epochs_f64(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_t n
 int eegfx_extract_features_f64(eegfx_ctx* ctx, const double* epochs, int64_t n, int32_t C,
                                int32_t name, int32_t epoch_size, int32_t skip,
                                int32_t feature_size, double* out, int mem);
+/* eegfx_extract_features_f64 on float32 epochs, float[n][C][750] (any 4-byte-aligned pointer):
+ * the rows are those of the f64 entry on the same epochs widened to double, bit for bit, under
+ * both numerics and for every feature size, skip and C it supports; the same argument checks,
+ * status codes, routes (device; small and large host batches, the large ones moving 2,048 bytes
+ * per window row over the host link) and guard counters. */
+int eegfx_extract_features_f32(eegfx_ctx* ctx, const float* epochs, int64_t n, int32_t C,
+                               int32_t name, int32_t epoch_size, int32_t skip,
+                               int32_t feature_size, double* out, int mem);
 
 /* The fused hot path: raw multiplexed recording -> dwt-8 feature matrix, without materialising
  * the epochs.  Equals eegfx_cut_epochs_f64 followed by eegfx_extract_features_f64 with
@@ -263,7 +283,7 @@ int eegfx_process_recording(eegfx_ctx* ctx, const void* raw, int32_t fmt, int64_
  * eegfx_cut_epochs_f64 followed by eegfx_extract_features_f64 with the same parameters (bit for
  * bit under EEGFX_EXACT; feature_size > 16 is EXACT in both settings, see there).  With
  * (8, 512, 175, 16) it is eegfx_process_recording itself, the fused kernels.  Every other
- * combination cuts the epochs into the context's scratch memory (6,000 C bytes per epoch) and
+ * combination cuts the epochs into the context's scratch memory (float32: 3,000 C bytes per epoch) and
  * extracts from them on the device, for every layout eegfx_cut_epochs_f64 accepts: a fused
  * kernel for wide rows measured slower than the two passes at feature_size 512 (DESIGN.md
  * 5.4.1).  Positions are validated as in
@@ -289,6 +309,14 @@ int eegfx_process_recording_epochs(eegfx_ctx* ctx, const void* raw, int32_t fmt,
                                    const float* res, int32_t C, const int64_t* pos,
                                    int64_t n_epochs, double* features, double* epochs_out,
                                    int mem);
+/* eegfx_process_recording_epochs with float32 epochs, float[n][C][750] (as eegfx_cut_epochs_f32:
+ * the fp32 values the f64 entry widens, any 4-byte-aligned pointer); `features` are the f64
+ * entry's rows, bit for bit.  The same layouts take the one pass and the two passes. */
+int eegfx_process_recording_epochs_f32(eegfx_ctx* ctx, const void* raw, int32_t fmt,
+                                       int64_t n_frames, int32_t n_channels_total,
+                                       const int32_t* cols, const float* res, int32_t C,
+                                       const int64_t* pos, int64_t n_epochs, double* features,
+                                       float* epochs_out, int mem);
 
 /* configs[4] -- long recordings streamed from host memory: raw (host, n_frames x
  * n_channels_total samples), pos and features are HOST arrays; the recording is moved to the device
@@ -422,6 +450,9 @@ const char* eegfx_odp_error(const eegfx_odp* odp);       /* "" when loading succ
 int64_t eegfx_odp_num_epochs(const eegfx_odp* odp);
 /* getData(): double[n][3][750] host copy */
 int eegfx_odp_get_data(const eegfx_odp* odp, double* out);
+/* eegfx_odp_get_data as float[n][3][750]: the resident double epochs narrowed on the device
+ * (exact: every value is a widened fp32), so half the bytes cross the host link. */
+int eegfx_odp_get_data_f32(const eegfx_odp* odp, float* out);
 /* getDataLabels(): double[n] */
 int eegfx_odp_get_labels(const eegfx_odp* odp, double* out);
 /* Selected marker positions (int64[n]) and source file index (int32[n]) of every epoch. */
