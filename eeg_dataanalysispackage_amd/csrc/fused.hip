@@ -10,8 +10,10 @@
 //
 // Two launches on one stream (DESIGN.md "Kernels"):
 //
-//  baseline_kernel  the 100 pre-stimulus frames of 64 epochs are staged in LDS with aligned
-//                   16-byte loads (all issued before the first wait); lane e of wave c folds
+//  baseline_kernel  the 100 pre-stimulus frames of 64 epochs are staged in LDS by LDS-DMA (one
+//                   16-byte-per-lane DMA per epoch, all issued before the one wait, no VGPR
+//                   staging; runs against the end of the recording go through registers,
+//                   zero-filled); lane e of wave c folds
 //                   (epoch e, channel c) sequentially in fp32 -- Baseline.java:29-42 is
 //                   order-exact, so this is deliberately not a tree reduction -- and writes
 //                   b[n][C] (12 B per epoch) and each epoch's window word (byte offset of the
@@ -102,26 +104,6 @@ __device__ __forceinline__ u32x4_a4 load16(const uint8_t* __restrict__ raw, int6
   return v;
 }
 
-// Issue-then-consume staging: the bulk load of an in-range quad is unconditional (an out-of-range
-// lane reads a placeholder quad and discards it), so the compiler batches every load of a thread
-// before the first wait; the rare quad that straddles the end of the recording is patched
-// afterwards by load16.  NT: non-temporal read, for pre-stimulus frames no other epoch's window
-// or baseline shares (baseline_kernel 0.136 -> 0.124 ms with markers 1,000 frames apart).
-template <bool NT = false>
-__device__ __forceinline__ u32x4_a4 load16_bulk(const uint8_t* __restrict__ raw, int64_t nbytes,
-                                                int64_t A, bool want) {
-  const bool full = want && A >= 0 && A + 16 <= nbytes;
-  const u32x4_a16* src = (const u32x4_a16*)(full ? raw + A : safe_quad(raw, nbytes));
-  u32x4_a4 v;
-  if constexpr (NT) v = __builtin_nontemporal_load(src);
-  else v = *src;
-  const u32x4_a4 z = {0u, 0u, 0u, 0u};
-  return full ? v : z;
-}
-__device__ __forceinline__ bool straddles_end(int64_t A, int64_t nbytes, bool want) {
-  return want && A >= 0 && A < nbytes && A + 16 > nbytes;
-}
-
 // Marker positions the reference cuts (OffLineDataProvider.java:220-225): copyOfRange(ch, pos-100,
 // pos+750) throws unless 0 <= pos-100 <= len.  Device-resident positions are checked here, where
 // the kernels read them anyway; a violation raises the context's error word (vector store to
@@ -139,6 +121,19 @@ __device__ __forceinline__ void flag_position(int* err) {
   if (err) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Pre-stimulus word of an epoch (LDS, baseline_kernel): the byte offset of its 100-frame run,
+// (pos - 100) * FB (even), with bit 0 set when the BASEQ quads from floor16 of it do not lie wholly
+// inside the recording (the guarded path).
+//
+// Staging is by LDS-DMA, as the windows' (dma_issue): wave w stages epochs w, w + NW, ... with one
+// global_load_lds_dwordx4 each -- lane q < BASEQ moves quad q from the scalar base floor16(run)
+// plus the per-lane constant 16 q to stage + e * BSTR + 4 q -- and every DMA of a wave leaves
+// before its one wait.  No VGPR holds a sample or an address.  An epoch whose quads reach past the
+// end of the recording (or a recording shorter than a quad) is filled through registers by load16
+// instead, zero outside the recording, so no read leaves [raw, raw + nbytes).
+// The fold reads (epoch e, frame i) with one ds_read_i16 per lane at dword e * BSTR + const:
+// BSTR = 157 = 29 (mod 32) is odd, so the 32 lanes of a half-wave fall on 32 distinct banks (up to
+// each epoch's sub-quad shift of at most 3 dwords, which can pair two lanes on a bank).
 template <int CT, int C, int TILE, bool STREAM = false>
 __global__ __launch_bounds__((TILE * C + 63) / 64 * 64) void baseline_kernel(
     const uint8_t* __restrict__ raw, int64_t n_frames, ChanSel sel, const int64_t* __restrict__ pos,
@@ -147,9 +142,13 @@ __global__ __launch_bounds__((TILE * C + 63) / 64 * 64) void baseline_kernel(
     unsigned long long* __restrict__ adapt, unsigned int* __restrict__ track_out) {
   using G = Geometry<CT>;
   constexpr int NT = (TILE * C + 63) / 64 * 64;
+  constexpr int NW = NT / 64;                  // waves
+  constexpr int PER_W = (TILE + NW - 1) / NW;  // epochs a wave stages (22 of 64)
+  static_assert(G::BASEQ <= 64 && PER_W <= 64, "one DMA per epoch, one lane per word");
   __shared__ __attribute__((aligned(16))) uint32_t stage[TILE * G::BSTR];
   __shared__ int64_t tB[TILE];
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t nbytes = n_frames * G::FB;
   const int64_t t0 = (int64_t)blockIdx.x * TILE;
   const int nt = (n - t0) < TILE ? (int)(n - t0) : TILE;
@@ -162,7 +161,8 @@ __global__ __launch_bounds__((TILE * C + 63) / 64 * 64) void baseline_kernel(
     const int64_t p = tid < nt ? pos[t0 + tid] : kPre;
     if (!position_ok(p, n_frames)) flag_position(err);
     const int64_t sp = safe_position(p, n_frames);
-    tB[tid] = (sp - kPre) * G::FB;
+    const int64_t R = (sp - kPre) * G::FB;  // >= 0
+    tB[tid] = R | (((R & ~(int64_t)15) + 16 * G::BASEQ <= nbytes) ? 0 : 1);
     if (tid < nt) {
       const int64_t B = (sp + 175) * G::FB;
       const int64_t Bq = B & ~(int64_t)15;
@@ -170,40 +170,46 @@ __global__ __launch_bounds__((TILE * C + 63) / 64 * 64) void baseline_kernel(
     }
   }
   __syncthreads();
-  constexpr int ITERS = (TILE * G::BASEQ + NT - 1) / NT;
-  u32x4_a4 v[ITERS];
-  int64_t A[ITERS];
-  bool want[ITERS];
-  const bool tiny = nbytes < 16;
+  // the words of this wave's epochs, lane t holding epoch w + NW t's: each becomes a scalar base
+  // with two v_readlane
+  const int el = w + NW * lane;
+  const int64_t wl = tB[el < TILE ? el : TILE - 1];
+  const int lo = (int)(uint32_t)wl, hi = (int)(uint32_t)((uint64_t)wl >> 32);
+  const bool active = lane < G::BASEQ;
+  // bit t: epoch w + NW t exists and is not guarded (a scalar mask: the loop's tests are uniform)
+  const uint64_t dma = __ballot(el < nt && (lo & 1) == 0);
+  const uint64_t fix = __ballot(el < nt && (lo & 1) != 0);
+  if (active) {
 #pragma unroll
-  for (int k = 0; k < ITERS; ++k) {
-    const int i = tid + k * NT;
-    const int e = i / G::BASEQ, q = i - e * G::BASEQ;
-    want[k] = i < TILE * G::BASEQ && e < nt;
-    A[k] = want[k] ? (tB[e] & ~(int64_t)15) + 16 * q : 0;
-    v[k] = load16_bulk<STREAM>(raw, nbytes, A[k], want[k] && !tiny);
-  }
-#pragma unroll
-  for (int k = 0; k < ITERS; ++k)
-    if (straddles_end(A[k], nbytes, want[k]) || (tiny && want[k])) v[k] = load16(raw, nbytes, A[k]);
-#pragma unroll
-  for (int k = 0; k < ITERS; ++k) {
-    const int i = tid + k * NT;
-    if (i < TILE * G::BASEQ) {
-      const int e = i / G::BASEQ, q = i - e * G::BASEQ;
-      lds_store4(stage + e * G::BSTR + 4 * q, v[k]);
+    for (int t = 0; t < PER_W; ++t) {
+      if ((dma >> t) & 1ull) {
+        const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane(lo, t);
+        const uint32_t whi = (uint32_t)__builtin_amdgcn_readlane(hi, t);
+        const int64_t Rq = (int64_t)(((uint64_t)whi << 32) | (wlo & ~15u));
+        dma16_s<STREAM>(raw + Rq, (uint32_t)(16 * lane), stage + (w + NW * t) * G::BSTR);
+      }
     }
   }
+  if (fix) {  // rare: a run against the end of the recording
+    for (int e = w; e < nt; e += NW) {
+      const int64_t W = tB[e];
+      if ((W & 1) && active)
+        lds_store4(stage + e * G::BSTR + 4 * lane,
+                   load16(raw, nbytes, (W & ~(int64_t)15) + 16 * lane));
+    }
+  }
+  dma_drain();
   __syncthreads();
   if (tid >= TILE * C) return;
   const int c = tid / TILE, e = tid - c * TILE;
+  if (e >= nt) return;
   const float r = sel.res[c];
-  const int16_t* src = (const int16_t*)((const uint8_t*)(stage + e * G::BSTR) + (tB[e] & 15)) +
+  const int16_t* src = (const int16_t*)((const uint8_t*)(stage + e * G::BSTR) + (tB[e] & 14)) +
                        sel.col[c];
   float b = 0.0f;
 #pragma unroll 20
   for (int i = 0; i < kPre; ++i) b = b + (float)src[i * CT] * r;
-  if (e < nt) bout[(t0 + e) * C + c] = b / (float)kPre;
+  bout[(t0 + e) * C + c] = b / (float)kPre;
 }
 
 
@@ -794,16 +800,17 @@ hipError_t launch_fused_baseline(hipStream_t st, const void* raw, int64_t n_fram
   unsigned int* track_out = adapt ? guard->track_out : nullptr;
   if (ct != 3 || C != 3) return hipErrorNotSupported;
   if (n == 0) return hipSuccess;
-  // 64 epochs per workgroup; 16/32/128 measured the same or slower.  Streaming
+  // 64 epochs per workgroup; 32 and 128 measured the same or slower.  Streaming
   // reads unless another epoch's window or baseline may share the pre-stimulus frames.
-  const dim3 g((unsigned)((n + 63) / 64));
+  constexpr int kTile = 64;
+  const dim3 g((unsigned)((n + kTile - 1) / kTile)), blk((kTile * 3 + 63) / 64 * 64);
   int64_t* words = (int64_t*)((uint8_t*)scratch + window_words_offset(n, C));
   if (streaming_reads(n_frames, n, dev::kPre + 687))
-    hipLaunchKernelGGL((dev::baseline_kernel<3, 3, 64, true>), g, dim3(192), 0, st,
+    hipLaunchKernelGGL((dev::baseline_kernel<3, 3, kTile, true>), g, blk, 0, st,
                        (const uint8_t*)raw, n_frames, sel, pos, n, (float*)scratch, words, err,
                        guard_count, rechecked, adapt, track_out);
   else
-    hipLaunchKernelGGL((dev::baseline_kernel<3, 3, 64>), g, dim3(192), 0, st, (const uint8_t*)raw,
+    hipLaunchKernelGGL((dev::baseline_kernel<3, 3, kTile>), g, blk, 0, st, (const uint8_t*)raw,
                        n_frames, sel, pos, n, (float*)scratch, words, err, guard_count, rechecked,
                        adapt, track_out);
   return hipGetLastError();

@@ -2,7 +2,7 @@
 # A/B of baseline_kernel variants: the baseline pass alone and the whole step
 # (PROBE_BASELINE / PROBE_STEP of window_probe), interleaved over two repetitions, then one
 # FETCH_SIZE pass per binary on baseline_kernel.
-#   VARIANTS="baseline32 baseline128" TAG=r04l bash tools/baseline_ab.sh
+#   VARIANTS="baseline32 baseline128 baseline_t128" TAG=r04l bash tools/baseline_ab.sh
 set -euo pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
