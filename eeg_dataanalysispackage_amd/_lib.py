@@ -63,6 +63,15 @@ class GatherOp(Structure):
 GATHER_SEND, GATHER_RECV, GATHER_COPY = 0, 1, 2
 
 
+class OdpShard(Structure):
+    _fields_ = [("ctx_index", c_int32), ("device", c_int32), ("first", c_int64),
+                ("count", c_int64), ("epochs", c_void_p), ("features", c_void_p),
+                ("features_numerics", c_int32)]
+
+
+ODP_MAX_SHARDS = 64
+
+
 class EegfxError(RuntimeError):
     """A non-zero status of the C ABI (carries the code and eegfx_last_error())."""
 
@@ -161,6 +170,11 @@ SIGNATURES = {
     "eegfx_odp_get_positions": (c_int, [c_void_p, c_void_p, c_void_p]),
     "eegfx_odp_get_features": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "eegfx_odp_destroy": (None, [c_void_p]),
+    "eegfx_odp_create_multi": (c_int, [POINTER(c_void_p), c_int32, POINTER(c_char_p), c_int32,
+                                       POINTER(c_void_p)]),
+    "eegfx_odp_num_shards": (c_int, [c_void_p]),
+    "eegfx_odp_get_shard": (c_int, [c_void_p, c_int32, POINTER(OdpShard)]),
+    "eegfx_shard_span": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
 }
 
 _lib = None

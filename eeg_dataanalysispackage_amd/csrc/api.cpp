@@ -226,7 +226,8 @@ struct eegfx_ctx {
   DevBuf raw, pos, out, scratch, fused;
   DevBuf lr_x, lr_y, lr_state, lr_part, lr_mask;  // logistic regression (eegfx_logreg_*)
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
-  PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings
+  PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
+                                         // a sharded provider's worker: the file spans it reads
   // The fma numerics' conditioning guard (guard.h): device memory holding the flagged-row count
   // of the current window_wide_kernel launch (first 128 B), then the running totals of recomputed
   // rows and of rows that went to the second stage, each spread over kGuardSlots lines; the
@@ -788,6 +789,28 @@ struct eegfx_odp {
   size_t d_features_cap = 0;
   int features_numerics = -1;  // -1: no resident rows (not all epochs have them)
 
+  // ---- a provider over several contexts (eegfx_odp_create_multi) --------------------------------
+  // `ctx` stays null: the planning pass is the planning-only provider's and also records, per
+  // file, what a shard needs to cut from it; the epochs then live in `shards`, one per context.
+  bool multi = false;
+  std::vector<eegfx_ctx*> ctxs;  // empty: planning-only
+  int32_t n_shards = 1;
+  struct FilePlan {
+    int32_t file_idx;
+    std::string eeg;
+    Header h;
+    int64_t n_frames;
+    int32_t idx[3];  // Fz, Cz, Pz as they stood at this file
+  };
+  std::vector<FilePlan> plans;
+  struct Shard {
+    int64_t first = 0, count = 0;
+    void* d_epochs = nullptr;    // double[count][3][750] on the shard's context, exact size
+    void* d_features = nullptr;  // double[count][48]
+    int numerics = -1;           // numerics of d_features' rows
+  };
+  std::vector<Shard> shards;
+
   void put_file(const std::string& k, int32_t v) {
     for (auto& kv : files)
       if (kv.first == k) {
@@ -891,6 +914,19 @@ struct eegfx_odp {
     return true;
   }
 
+  // columns and resolutions of Fz, Cz, Pz (1-based channel numbers) in a recording
+  static ChanSel file_sel(const Header& h, const int32_t idx[3]) {
+    int32_t cols[3];
+    float res[3];
+    for (int c = 0; c < 3; ++c) {
+      cols[c] = idx[c] - 1;
+      res[c] = 1.0f;
+      for (const auto& ci : h.channels)
+        if (ci.number == idx[c]) res[c] = (float)ci.resolution;
+    }
+    return make_sel(cols, res, 3, h.info.n_channels);
+  }
+
   void append_epochs(const Header& h, int64_t n_frames, const void* d_raw,
                      const std::vector<int64_t>& pos, int32_t file_idx,
                      const std::vector<double>& lab) {
@@ -904,16 +940,8 @@ struct eegfx_odp {
       return;
     }
     const int ct = h.info.n_channels;
-    int32_t cols[3];
-    float res[3];
     const int32_t idx[3] = {fz_index, cz_index, pz_index};
-    for (int c = 0; c < 3; ++c) {
-      cols[c] = idx[c] - 1;
-      res[c] = 1.0f;
-      for (const auto& ci : h.channels)
-        if (ci.number == idx[c]) res[c] = (float)ci.resolution;
-    }
-    const ChanSel sel = make_sel(cols, res, 3, ct);
+    const ChanSel sel = file_sel(h, idx);
     const size_t per = sizeof(double) * 3 * EEGFX_POSTSTIMULUS;
     // grow the resident epoch buffer (copy-on-grow)
     const size_t need = per * (size_t)(n_epochs + k);
@@ -977,6 +1005,7 @@ struct eegfx_odp {
           fail(EEGFX_EINVAL, "%s: channel %s not found (index %d)", vhdr_file.c_str(),
                c == 0 ? "Fz" : c == 1 ? "Cz" : "Pz", sel[c]);
       const int64_t n_frames = recording_frames(h, eeg_file);
+      if (multi) plans.push_back(FilePlan{file_idx, eeg_file, h, n_frames, {sel[0], sel[1], sel[2]}});
       const size_t raw_bytes =
           (size_t)n_frames * h.info.n_channels * sample_bytes(h.info.binary_format);
       void* d_raw = nullptr;
@@ -1000,6 +1029,212 @@ struct eegfx_odp {
       append_epochs(h, n_frames, d_raw, pos, file_idx, lab);  // epochs accepted before an error
       if (rc != EEGFX_OK) fail(rc, "%s", last_error().c_str());
     }
+  }
+
+  // ---- several contexts: plan once on the host, then one worker per context ---------------------
+  void release_shards() {
+    for (size_t r = 0; r < shards.size() && r < ctxs.size(); ++r) {
+      Shard& s = shards[r];
+      if (!s.d_epochs && !s.d_features) continue;
+      (void)hipSetDevice(ctxs[r]->device);
+      if (s.d_epochs) (void)hipFreeAsync(s.d_epochs, ctxs[r]->stream);
+      if (s.d_features) (void)hipFreeAsync(s.d_features, ctxs[r]->stream);
+      (void)hipStreamSynchronize(ctxs[r]->stream);
+      s.d_epochs = s.d_features = nullptr;
+    }
+  }
+
+  // Shard r: eegfx_shard_range(planned, r, n_shards) clipped to the first `kept` epochs.
+  void set_ranges(int64_t planned, int64_t kept) {
+    for (int32_t r = 0; r < n_shards; ++r) {
+      int64_t a = 0, b = 0;
+      if (eegfx_shard_range(planned, r, n_shards, &a, &b) != EEGFX_OK)
+        fail(EEGFX_EINVAL, "%s", last_error().c_str());
+      shards[(size_t)r].first = std::min(a, kept);
+      shards[(size_t)r].count = std::min(b, kept) - std::min(a, kept);
+    }
+  }
+
+  struct WorkerError {
+    int code = EEGFX_OK;
+    int32_t file = -1;  // index (in `files`) of the file the worker was on
+    std::string text;
+  };
+
+  // The worker of context r: the files its range intersects, in order; of each, the frames
+  // eegfx_shard_span names, through two pinned staging buffers (the read of one file overlaps the
+  // upload and the kernels of the one before), into the epochs' slots of the shard's buffers.
+  void run_shard(size_t r, const std::vector<int32_t>& plan_of_file, WorkerError* we) {
+    eegfx_ctx* c = ctxs[r];
+    Shard& s = shards[r];
+    int32_t cur_file = file_of_epoch[(size_t)s.first];
+    struct Events {
+      hipEvent_t e[2] = {nullptr, nullptr};
+      ~Events() {
+        for (hipEvent_t x : e)
+          if (x) (void)hipEventDestroy(x);
+      }
+    } staged;
+    bool used[2] = {false, false};
+    try {
+      c->activate();
+      const size_t per = sizeof(double) * 3 * EEGFX_POSTSTIMULUS;
+      const size_t fper = sizeof(double) * 3 * EEGFX_DWT8_FEATURE_SIZE;
+      HIP_CHECK(hipMallocAsync(&s.d_epochs, per * (size_t)s.count, c->stream));
+      HIP_CHECK(hipMallocAsync(&s.d_features, fper * (size_t)s.count, c->stream));
+      s.numerics = c->numerics;
+      for (hipEvent_t& x : staged.e) HIP_CHECK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+      const int64_t end = s.first + s.count;
+      int b = 0;
+      for (int64_t i = s.first; i < end; b ^= 1) {
+        const int32_t f = file_of_epoch[(size_t)i];
+        cur_file = f;
+        int64_t j = i;
+        while (j < end && file_of_epoch[(size_t)j] == f) ++j;
+        const int64_t k = j - i;
+        const FilePlan& fp = plans[(size_t)plan_of_file[(size_t)f]];
+        int64_t first = 0, frames = 0;
+        if (eegfx_shard_span(&positions[(size_t)i], k, fp.n_frames, &first, &frames) != EEGFX_OK)
+          fail(EEGFX_EINVAL, "%s", last_error().c_str());
+        // pos - 100 == n_frames for every epoch of the span: one frame earlier, so that no kernel
+        // is launched on an empty recording (a recording of no frames at all stays empty, as it
+        // is for the one-context provider)
+        if (frames == 0 && first > 0) {
+          --first;
+          frames = 1;
+        }
+        const int ct = fp.h.info.n_channels;
+        const size_t raw_bytes = (size_t)frames * ct * sample_bytes(fp.h.info.binary_format);
+        const size_t pos_off = (raw_bytes + 7) & ~(size_t)7;
+        if (used[b]) HIP_CHECK(hipEventSynchronize(staged.e[b]));  // its last upload has left it
+        char* host = (char*)c->pin_chunk[b].get(pos_off + sizeof(int64_t) * (size_t)k);
+        read_recording_span(fp.h, fp.eeg, host, fp.n_frames, first, frames);
+        int64_t* h_pos = (int64_t*)(host + pos_off);
+        for (int64_t t = 0; t < k; ++t) h_pos[t] = positions[(size_t)(i + t)] - first;
+        void* d_raw = c->raw.get(raw_bytes);
+        if (raw_bytes)
+          HIP_CHECK(hipMemcpyAsync(d_raw, host, raw_bytes, hipMemcpyHostToDevice, c->stream));
+        int64_t* d_pos = (int64_t*)c->pos.get(sizeof(int64_t) * (size_t)k);
+        HIP_CHECK(hipMemcpyAsync(d_pos, h_pos, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice,
+                                 c->stream));
+        HIP_CHECK(hipEventRecord(staged.e[b], c->stream));
+        used[b] = true;
+        run_epochs_and_features(c, d_raw, fp.h.info.binary_format, frames, ct,
+                                file_sel(fp.h, fp.idx), 3, d_pos, k,
+                                (double*)((char*)s.d_epochs + per * (size_t)(i - s.first)),
+                                (double*)((char*)s.d_features + fper * (size_t)(i - s.first)));
+        i = j;
+      }
+      c->drain();
+    } catch (const Error& e) {
+      *we = WorkerError{e.code, cur_file, e.what()};
+    } catch (const std::bad_alloc&) {
+      *we = WorkerError{EEGFX_ENOMEM, cur_file, "out of host memory"};
+    } catch (const std::exception& e) {
+      *we = WorkerError{EEGFX_EINVAL, cur_file, e.what()};
+    }
+    // after a failure copies may still read the staging buffers: nothing is left in flight
+    if (we->code != EEGFX_OK) (void)hipStreamSynchronize(c->stream);
+  }
+
+  // Runs the workers and joins them; the failure in the earliest file, if any.
+  WorkerError compute() {
+    std::vector<int32_t> plan_of_file(files.size(), -1);
+    for (size_t p = 0; p < plans.size(); ++p) plan_of_file[(size_t)plans[p].file_idx] = (int32_t)p;
+    std::vector<WorkerError> errs(shards.size());
+    {
+      Joiner workers;
+      for (size_t r = 0; r < shards.size(); ++r)
+        if (shards[r].count > 0)
+          workers.th.emplace_back([this, r, &plan_of_file, &errs] {
+            run_shard(r, plan_of_file, &errs[r]);
+          });
+    }
+    WorkerError worst;
+    for (const WorkerError& e : errs)
+      if (e.code != EEGFX_OK && (worst.code == EEGFX_OK || e.file < worst.file)) worst = e;
+    return worst;
+  }
+
+  int load_multi() {
+    int rc = guarded([&] {
+      release_shards();
+      shards.assign((size_t)n_shards, Shard());
+      files.clear();
+      plans.clear();
+      labels.clear();
+      positions.clear();
+      file_of_epoch.clear();
+      file_prefix.clear();
+      n_epochs = epochs_counter = balance = 0;
+      fz_index = cz_index = pz_index = 0;
+      for (size_t r = 1; r < ctxs.size(); ++r)
+        if (ctxs[r]->numerics != ctxs[0]->numerics)
+          fail(EEGFX_EINVAL,
+               "the contexts of a provider must hold the same numerics at loadData (context %d "
+               "holds %d, context 0 holds %d)", (int)r, ctxs[r]->numerics, ctxs[0]->numerics);
+      handle_input();
+      process_eeg_files();  // ctx == nullptr: the planning pass, in file order
+    });
+    std::string text = rc == EEGFX_OK ? "" : last_error();
+    const int64_t planned = n_epochs;
+    const int rc2 = guarded([&] {
+      set_ranges(planned, planned);
+      if (ctxs.empty() || planned == 0) return;
+      WorkerError w;
+      try {
+        w = compute();
+      } catch (const std::exception& e) {  // no worker ran to its end: nothing is kept
+        w = WorkerError{EEGFX_EINVAL, 0, e.what()};
+      }
+      if (w.code == EEGFX_OK) return;
+      // the one-context provider would have stopped in that file: the files before it stay
+      const int64_t kept =
+          std::lower_bound(file_of_epoch.begin(), file_of_epoch.end(), w.file) -
+          file_of_epoch.begin();
+      positions.resize((size_t)kept);
+      labels.resize((size_t)kept);
+      file_of_epoch.resize((size_t)kept);
+      n_epochs = kept;
+      set_ranges(planned, kept);
+      fail(w.code, "%s", w.text.c_str());
+    });
+    if (rc2 != EEGFX_OK) {
+      rc = rc2;
+      text = last_error();
+    }
+    error = text;
+    set_last_error(text);
+    return rc;
+  }
+
+  // An accessor's work on every shard that holds epochs: `enqueue(ctx, shard)` on each context's
+  // stream first, then every context is drained, so the devices work at the same time.  Whatever
+  // was enqueued is drained even when a later step fails (it writes into the caller's buffer).
+  template <typename F>
+  void on_shards(F&& enqueue) const {
+    size_t started = 0;
+    std::unique_ptr<Error> first;
+    try {
+      for (; started < shards.size(); ++started) {
+        if (shards[started].count == 0) continue;
+        ctxs[started]->activate();
+        enqueue(ctxs[started], shards[started]);
+      }
+    } catch (const Error& e) {
+      first.reset(new Error(e));
+      started = std::min(started + 1, shards.size());
+    }
+    for (size_t r = 0; r < started; ++r) {
+      if (shards[r].count == 0) continue;
+      try {
+        ctxs[r]->activate();
+        ctxs[r]->drain();
+      } catch (const Error& e) {
+        if (!first) first.reset(new Error(e));
+      }
+    }
+    if (first) throw *first;
   }
 };
 
@@ -1957,6 +2192,7 @@ int eegfx_odp_load_data(eegfx_odp* odp) {
     set_last_error("null provider");
     return EEGFX_EINVAL;
   }
+  if (odp->multi) return odp->load_multi();
   // loadData (:88-98): every exception is logged as fatal and swallowed; what was loaded stays.
   const int rc = guarded([&] {
     if (odp->ctx) odp->ctx->activate();
@@ -1975,6 +2211,14 @@ int eegfx_odp_get_data(const eegfx_odp* odp, double* out) {
   return guarded([&] {
     if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
     if (!odp->n_epochs) return;
+    if (odp->multi && !odp->ctxs.empty()) {
+      const size_t per = sizeof(double) * 3 * EEGFX_POSTSTIMULUS;
+      odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
+        HIP_CHECK(hipMemcpyAsync((char*)out + per * (size_t)s.first, s.d_epochs,
+                                 per * (size_t)s.count, hipMemcpyDeviceToHost, ctx->stream));
+      });
+      return;
+    }
     if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
     odp->ctx->activate();
     HIP_CHECK(hipMemcpyAsync(out, odp->d_epochs,
@@ -1988,6 +2232,17 @@ int eegfx_odp_get_data_f32(const eegfx_odp* odp, float* out) {
   return guarded([&] {
     if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
     if (!odp->n_epochs) return;
+    if (odp->multi && !odp->ctxs.empty()) {
+      odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
+        const int64_t count = 3 * EEGFX_POSTSTIMULUS * s.count;
+        float* d_f32 = (float*)ctx->scratch.get(sizeof(float) * (size_t)count);
+        HIP_CHECK(launch_narrow_epochs(ctx->stream, (const double*)s.d_epochs, d_f32, count));
+        HIP_CHECK(hipMemcpyAsync(out + 3 * EEGFX_POSTSTIMULUS * s.first, d_f32,
+                                 sizeof(float) * (size_t)count, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+      });
+      return;
+    }
     if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
     eegfx_ctx* ctx = odp->ctx;
     ctx->activate();
@@ -2023,6 +2278,30 @@ int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int
     if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
     check_fe_params(3, name, epoch_size, skip, feature_size);
     if (!odp->n_epochs) return;
+    if (odp->multi && !odp->ctxs.empty()) {
+      const size_t row = sizeof(double) * 3 * (size_t)feature_size;
+      odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
+        char* dst = (char*)out + row * (size_t)s.first;
+        const size_t bytes = row * (size_t)s.count;
+        if (skip == EEGFX_DWT8_SKIP && feature_size == EEGFX_DWT8_FEATURE_SIZE &&
+            s.numerics == ctx->numerics && s.d_features) {
+          HIP_CHECK(hipMemcpyAsync(dst, s.d_features, bytes, hipMemcpyDeviceToHost, ctx->stream));
+          return;
+        }
+        double* d_out = (double*)ctx->out.get(bytes);
+        if (wide_features(feature_size)) {
+          HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)s.d_epochs, s.count, 3,
+                                               skip, feature_size, d_out, EEGFX_POSTSTIMULUS));
+        } else {
+          const Guard g = ctx->guard_for(s.count);
+          HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)s.d_epochs, s.count, 3,
+                                                skip, feature_size, ctx->numerics != EEGFX_EXACT,
+                                                d_out, EEGFX_POSTSTIMULUS, g));
+        }
+        HIP_CHECK(hipMemcpyAsync(dst, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+      });
+      return;
+    }
     if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
     eegfx_ctx* ctx = odp->ctx;
     ctx->activate();
@@ -2052,8 +2331,84 @@ int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int
   });
 }
 
+int eegfx_odp_create_multi(eegfx_ctx* const* ctxs, int32_t n_ctx, const char* const* args,
+                           int32_t n_args, eegfx_odp** out) {
+  return guarded([&] {
+    if (!out || (n_args > 0 && !args) || n_args < 0) fail(EEGFX_EINVAL, "null argument");
+    if (n_ctx < 1 || n_ctx > EEGFX_ODP_MAX_SHARDS)
+      fail(EEGFX_EINVAL, "%d contexts outside [1, %d]", n_ctx, EEGFX_ODP_MAX_SHARDS);
+    std::unique_ptr<eegfx_odp> o(new eegfx_odp());
+    o->multi = true;
+    o->n_shards = n_ctx;
+    for (int i = 0; ctxs && i < n_ctx; ++i) {
+      if (!ctxs[i]) fail(EEGFX_EINVAL, "context %d is null", i);
+      for (int j = 0; j < i; ++j)
+        if (ctxs[j] == ctxs[i])
+          fail(EEGFX_EINVAL, "context %d repeats context %d: two shards would share its buffers", i,
+               j);
+      o->ctxs.push_back(ctxs[i]);
+    }
+    o->shards.assign((size_t)n_ctx, eegfx_odp::Shard());
+    for (int i = 0; i < n_args; ++i) o->args.emplace_back(args[i] ? args[i] : "");
+    *out = o.release();
+  });
+}
+
+int eegfx_odp_num_shards(const eegfx_odp* odp) { return odp ? odp->n_shards : 0; }
+
+int eegfx_odp_get_shard(const eegfx_odp* odp, int32_t i, eegfx_odp_shard* out) {
+  return guarded([&] {
+    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
+    if (i < 0 || i >= odp->n_shards)
+      fail(EEGFX_EINVAL, "shard %d outside [0, %d)", i, odp->n_shards);
+    eegfx_odp_shard v = {i, -1, 0, 0, nullptr, nullptr, -1};
+    if (odp->multi) {
+      const eegfx_odp::Shard& s = odp->shards[(size_t)i];
+      v.first = s.first;
+      v.count = s.count;
+      if (!odp->ctxs.empty()) {
+        v.device = odp->ctxs[(size_t)i]->device;
+        if (s.count > 0) {
+          v.epochs = (const double*)s.d_epochs;
+          v.features = (const double*)s.d_features;
+          v.features_numerics = s.d_features ? s.numerics : -1;
+        }
+      }
+    } else {
+      v.count = odp->n_epochs;
+      if (odp->ctx) {
+        v.device = odp->ctx->device;
+        if (odp->n_epochs > 0) {
+          v.epochs = (const double*)odp->d_epochs;
+          if (odp->features_numerics >= 0 && odp->d_features) {
+            v.features = (const double*)odp->d_features;
+            v.features_numerics = odp->features_numerics;
+          }
+        }
+      }
+    }
+    *out = v;
+  });
+}
+
+int eegfx_shard_span(const int64_t* pos, int64_t n, int64_t n_frames, int64_t* first_frame,
+                     int64_t* frames) {
+  return guarded([&] {
+    if (n < 0 || n_frames < 0 || (n > 0 && !pos) || !first_frame || !frames)
+      fail(EEGFX_EINVAL, "shard_span(n=%lld, n_frames=%lld)", (long long)n, (long long)n_frames);
+    *first_frame = *frames = 0;
+    if (n == 0) return;
+    const auto mm = std::minmax_element(pos, pos + n);
+    check_positions(mm.first, 1, n_frames);
+    check_positions(mm.second, 1, n_frames);
+    *first_frame = *mm.first - EEGFX_PRESTIMULUS;
+    *frames = std::min(n_frames, *mm.second + EEGFX_POSTSTIMULUS) - *first_frame;
+  });
+}
+
 void eegfx_odp_destroy(eegfx_odp* odp) {
   if (!odp) return;
+  odp->release_shards();
   if (odp->ctx && (odp->d_epochs || odp->d_features)) {
     (void)hipSetDevice(odp->ctx->device);
     if (odp->d_epochs) (void)hipFreeAsync(odp->d_epochs, odp->ctx->stream);

@@ -327,6 +327,53 @@ void read_recording(const Header& h, const std::string& path, void* dst, int64_t
   }
 }
 
+// Frames [first, first + frames) of the recording as multiplexed frames: one contiguous byte range
+// of a MULTIPLEXED file, the same frame range of every channel of a VECTORIZED one (interleaved as
+// read_recording does).  The payload outside the range is not read.
+void read_recording_span(const Header& h, const std::string& path, void* dst, int64_t n_frames,
+                         int64_t first, int64_t frames) {
+  const int64_t sb = sample_bytes(h.info.binary_format), nc = h.info.n_channels;
+  if (first < 0 || frames < 0 || first + frames > n_frames)
+    fail(EEGFX_EINVAL, "frames [%lld, %lld) outside the %lld of %s", (long long)first,
+         (long long)(first + frames), (long long)n_frames, path.c_str());
+  if (frames == 0) return;
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) fail(EEGFX_EIO, "cannot open %s", path.c_str());
+  auto read_at = [&](int64_t off, void* to, int64_t nbytes) {
+    int64_t got = 0;
+    if (fseeko(f, (off_t)off, SEEK_SET) == 0) {
+      while (got < nbytes) {
+        const size_t r = fread((char*)to + got, 1, (size_t)(nbytes - got), f);
+        if (r == 0) break;
+        got += (int64_t)r;
+      }
+    }
+    if (got != nbytes) {
+      fclose(f);
+      fail(EEGFX_EIO, "short read on %s (%lld of %lld bytes at offset %lld)", path.c_str(),
+           (long long)got, (long long)nbytes, (long long)off);
+    }
+  };
+  if (h.info.multiplexed) {
+    read_at(first * nc * sb, dst, frames * nc * sb);
+  } else {
+    std::vector<char> v;
+    try {
+      v.resize((size_t)(frames * sb));
+    } catch (...) {
+      fclose(f);
+      throw;
+    }
+    char* out = (char*)dst;
+    for (int64_t c = 0; c < nc; ++c) {
+      read_at((c * n_frames + first) * sb, v.data(), frames * sb);
+      for (int64_t t = 0; t < frames; ++t)
+        memcpy(out + (t * nc + c) * sb, v.data() + t * sb, (size_t)sb);
+    }
+  }
+  fclose(f);
+}
+
 }  // namespace eegfx
 
 using namespace eegfx;

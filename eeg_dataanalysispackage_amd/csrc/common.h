@@ -69,6 +69,9 @@ bool file_exists(const std::string& path);
 void read_file_bytes(const std::string& path, void* dst, int64_t nbytes);
 // n_frames multiplexed frames of the recording (a VECTORIZED file is interleaved on the host).
 void read_recording(const Header& h, const std::string& path, void* dst, int64_t n_frames);
+// Frames [first, first + frames) of it, multiplexed likewise; nothing outside the range is read.
+void read_recording_span(const Header& h, const std::string& path, void* dst, int64_t n_frames,
+                         int64_t first, int64_t frames);
 // Java Integer.parseInt semantics (optional sign, ASCII digits, int32 range); false on failure.
 bool java_parse_int(const std::string& s, int32_t* out);
 // Java String.split(" ") semantics (trailing empty strings removed).

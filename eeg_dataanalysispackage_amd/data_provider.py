@@ -8,6 +8,11 @@ and exposes the message as ``last_error``.  Paths are local files (the reference
 
 Decode, epoch cut and baseline correction run on the GPU (csrc/kernels.hip); the epochs stay
 resident in HBM and ``getData()`` copies them back.
+
+``OffLineDataProvider(args, contexts=[...])`` shards ``loadData()`` over several contexts (any mix
+of devices): one host planning pass, then one worker per context on its ``shard_range`` slice of
+the selected epochs.  The getters return the same rows in the same order; ``getShards()`` exposes
+each shard's resident device buffers (include/eegfx.h, eegfx_odp_create_multi).
 """
 from __future__ import annotations
 
@@ -24,19 +29,86 @@ from .context import Context
 log = logging.getLogger(__name__)
 
 
+class _DeviceView:
+    """A device array of a shard (``__cuda_array_interface__`` version 2, float64):
+    ``torch.as_tensor(view, device="cuda")`` wraps it without a copy.  The memory belongs to the
+    provider and is read-only by contract -- nothing may write through the view.  The interface's
+    read-only flag stays False all the same: torch refuses an array that sets it ("the read only
+    flag is not supported"), and a view nobody can wrap would serve no one.  Valid until the
+    provider's next ``loadData()`` or ``close()``; keeps the provider alive."""
+
+    read_only = True
+
+    def __init__(self, owner, address, shape):
+        self._owner = owner
+        self.shape = tuple(shape)
+        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": "<f8",
+                                         "data": (int(address or 0), False), "version": 2,
+                                         "strides": None}
+
+
+class Shard:
+    """One shard of a provider (eegfx_odp_shard): the epochs ``[first, first + count)`` of
+    ``getData()`` order, resident on context ``ctx_index`` (HIP device ``device``, -1 for a
+    planning-only provider).  ``epochs`` (count, 3, 750) and ``features`` (count, 48) are device
+    views; ``features_numerics`` is EXACT / FMA of those rows, -1 when there are none."""
+
+    def __init__(self, owner, s):
+        self.ctx_index, self.device = int(s.ctx_index), int(s.device)
+        self.first, self.count = int(s.first), int(s.count)
+        self.features_numerics = int(s.features_numerics)
+        self.epochs = _DeviceView(owner, s.epochs, (self.count if s.epochs else 0, 3,
+                                                    _lib.POSTSTIMULUS))
+        self.features = _DeviceView(owner, s.features, (self.count if s.features else 0, 48))
+
+    def __repr__(self):
+        return (f"Shard(ctx_index={self.ctx_index}, device={self.device}, first={self.first}, "
+                f"count={self.count}, features_numerics={self.features_numerics})")
+
+
 class OffLineDataProvider:
     def __init__(self, args: Sequence[str], context: Optional[Context] = None,
-                 plan_only: bool = False):
-        """plan_only=True: parse, select and label on the host only (no GPU, no epochs)."""
+                 plan_only: bool = False, contexts: Optional[Sequence[Context]] = None,
+                 shards: Optional[int] = None):
+        """plan_only=True: parse, select and label on the host only (no GPU, no epochs).
+        contexts=[Context, ...]: a provider over several contexts (eegfx_odp_create_multi), any
+        mix of devices; loadData() shards the selected epochs over them (getShards()).
+        plan_only=True, shards=k: the planning-only provider that reports the same k ranges."""
         self.args = list(args)
-        self._ctx = None if plan_only else (context if context is not None else Context())
         argv = (ctypes.c_char_p * max(1, len(self.args)))(*[a.encode() for a in self.args])
         h = ctypes.c_void_p()
-        handle = self._ctx.handle if self._ctx is not None else None
-        check(lib().eegfx_odp_create(handle, argv, len(self.args), ctypes.byref(h)))
+        if contexts is not None or shards is not None:
+            if context is not None:
+                raise ValueError("give either context or contexts")
+            if plan_only:
+                if contexts is not None or shards is None:
+                    raise ValueError("a planning-only sharded provider takes shards=k, no contexts")
+                self._ctxs, n, handles = [], int(shards), None
+            else:
+                if contexts is None or (shards is not None and shards != len(contexts)):
+                    raise ValueError("shards must equal len(contexts)")
+                self._ctxs = list(contexts)
+                n = len(self._ctxs)
+                handles = (ctypes.c_void_p * max(1, n))(*[c.handle for c in self._ctxs])
+            self._ctx = None
+            check(lib().eegfx_odp_create_multi(handles, n, argv, len(self.args), ctypes.byref(h)))
+        else:
+            self._ctx = None if plan_only else (context if context is not None else Context())
+            self._ctxs = [] if self._ctx is None else [self._ctx]
+            handle = self._ctx.handle if self._ctx is not None else None
+            check(lib().eegfx_odp_create(handle, argv, len(self.args), ctypes.byref(h)))
         self._h = h
         self.last_error = ""
         log.info("Started OffLineDataProvider with arguments %s", self.args)
+
+    def getShards(self) -> List[Shard]:
+        """The provider's shards in list order (one for a one-context provider)."""
+        out = []
+        for i in range(int(lib().eegfx_odp_num_shards(self._h))):
+            s = _lib.OdpShard()
+            check(lib().eegfx_odp_get_shard(self._h, i, ctypes.byref(s)))
+            out.append(Shard(self, s))
+        return out
 
     def loadData(self) -> None:
         rc = lib().eegfx_odp_load_data(self._h)

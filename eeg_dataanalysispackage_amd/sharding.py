@@ -105,6 +105,20 @@ def native_shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
     return s.value, e.value
 
 
+def shard_span(pos, n_frames: int) -> Tuple[int, int]:
+    """eegfx_shard_span through the C ABI: (first_frame, frames) of the recording that the epochs
+    at marker positions `pos` (any order) touch -- min(pos) - 100 up to
+    min(n_frames, max(pos) + 750); (0, 0) for no positions."""
+    import numpy as np
+    from ctypes import byref, c_int64
+    from ._lib import check, lib, ptr
+    p = np.ascontiguousarray(pos, dtype=np.int64).reshape(-1)
+    first, frames = c_int64(), c_int64()
+    check(lib().eegfx_shard_span(ptr(p) if p.size else None, p.size, n_frames, byref(first),
+                                 byref(frames)))
+    return first.value, frames.value
+
+
 class Comm:
     """An RCCL communicator bound to a Context (eegfx_comm_* in include/eegfx.h).
 

@@ -462,6 +462,66 @@ int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int
                            int32_t feature_size, double* out);
 void eegfx_odp_destroy(eegfx_odp* odp);
 
+/* ---- OffLineDataProvider over several contexts ----------------------------------------------
+ * A provider over n_ctx contexts (1..EEGFX_ODP_MAX_SHARDS), any mix of devices, each context at
+ * most once (a repeated context: EEGFX_EINVAL, as two shards would share its scratch buffers).
+ * ctxs == NULL with n_ctx >= 1: a planning-only provider that reports the same shard ranges and
+ * touches no GPU and no sample payload.
+ *
+ * eegfx_odp_load_data on such a provider works in two phases.  It first plans on the host, once
+ * and in file order, exactly as the planning-only provider does (headers, the Fz/Cz/Pz indices
+ * and the target / non-target balance carried across files, markers): the whole selected-epoch
+ * list.  Context r then owns the epochs eegfx_shard_range(n, r, n_ctx) of that list -- the
+ * partition eegfx_gather_root expects of rank r, so a shard's `features` is a valid `local`
+ * argument for it.  One worker thread per context that has epochs walks the files its range
+ * intersects, reads only the frames eegfx_shard_span names for its positions in each file,
+ * uploads them and runs the one-pass kernels on its context's stream, into resident buffers
+ * allocated once at their exact size.  Every context has been drained when load_data returns.
+ *
+ * All contexts must hold the same numerics at load_data (else EEGFX_EINVAL, nothing is loaded).
+ * The call starts over: what an earlier load_data of the provider left is released first.
+ * After the call num_epochs, positions, labels, file indices, the return code and the
+ * eegfx_odp_error text equal those of eegfx_odp_create's provider on the same arguments (bit for
+ * bit under EEGFX_EXACT; within the fma contract under EEGFX_FMA, whose guard strategy is
+ * per-context state).  A failure a worker meets in file j (a payload read, a HIP error)
+ * overrides an error planning found in file j or later and keeps only the epochs of the files
+ * before j; the shard ranges are then the planned ranges clipped to what is kept -- the one
+ * exception to the balanced partition.
+ *
+ * eegfx_odp_get_data / _get_data_f32 / _get_labels / _get_positions / _get_features return rows
+ * in list order: each shard does the one-context work on its own context, straight into rows
+ * [first, first + count) of the caller's buffer, enqueued on every context before any is
+ * drained.  eegfx_odp_destroy frees every shard on its own device.  The threading rule of a
+ * context extends to the provider: no other call may use one of its contexts during a call on
+ * the provider. */
+#define EEGFX_ODP_MAX_SHARDS 64
+int eegfx_odp_create_multi(eegfx_ctx* const* ctxs, int32_t n_ctx, const char* const* args,
+                           int32_t n_args, eegfx_odp** out);
+
+/* The device view of one shard.  The pointers stay valid until the next eegfx_odp_load_data or
+ * eegfx_odp_destroy of the provider and are complete when eegfx_odp_load_data returns.
+ * eegfx_odp_create's provider has one shard: its own resident buffers. */
+typedef struct {
+  int32_t ctx_index;         /* index into ctxs                                                 */
+  int32_t device;            /* HIP device of that context; -1 for a planning-only provider      */
+  int64_t first, count;      /* the shard's epochs in getData() order                            */
+  const double* epochs;      /* device, double[count][3][750]; NULL if count == 0 / planning     */
+  const double* features;    /* device, double[count][48], rows of (8,512,175,16) computed at
+                                loadData; NULL if count == 0 / planning / not resident           */
+  int32_t features_numerics; /* EEGFX_EXACT | EEGFX_FMA of those rows, -1 if features == NULL    */
+} eegfx_odp_shard;
+int eegfx_odp_num_shards(const eegfx_odp* odp);   /* 1 for eegfx_odp_create's provider */
+int eegfx_odp_get_shard(const eegfx_odp* odp, int32_t i, eegfx_odp_shard* out);
+
+/* Pure host function: the frames a shard's epochs of one recording touch.
+ * first_frame = min(pos) - 100, frames = min(n_frames, max(pos) + 750) - first_frame
+ * (positions in any order, each with pos - 100 in [0, n_frames]; n == 0 gives 0, 0).  An epoch
+ * cut from the span with positions rebased by first_frame and n_frames = frames equals the one
+ * cut from the whole recording: the span keeps the recording's end, so the zero padding past it
+ * is the same. */
+int eegfx_shard_span(const int64_t* pos, int64_t n, int64_t n_frames, int64_t* first_frame,
+                     int64_t* frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,324 @@
+"""The OffLineDataProvider over several contexts (eegfx_odp_create_multi) against the one-context
+provider on the same arguments: bit for bit under EXACT numerics -- epochs, float32 epochs,
+labels, positions, file indices, features, return code and error text -- and against the oracle.
+
+Context i is created on device i % eegfx_device_count(): on a box that shows one GPU every
+context shares that device, so everything is exercised except the change of device between
+shards (hipSetDevice to another GPU in the workers and in the accessors)."""
+import numpy as np
+import pytest
+
+import eeg_dataanalysispackage_amd as fx
+from eeg_dataanalysispackage_amd import _lib
+from eeg_dataanalysispackage_amd.sharding import native_shard_range
+from conftest import (DOD01, DOD02, EPOCH_SUM_GOLDEN, FEATURE_SUM_GOLDEN, INFO_TRAIN, hexrows)
+from odp_multi_data import synthetic_directory, two_file_info
+from oracle import oracle
+
+pytestmark = pytest.mark.gpu
+FMA_TOL = 1e-9  # the library's fma contract, the tolerance of tests/test_gpu_parity.py
+
+
+def eq(a, b):
+    return np.array_equal(a, b, equal_nan=True)
+
+
+def make_contexts(k, numerics="exact"):
+    n_dev = fx.device_count()
+    return [fx.Context(i % n_dev, numerics=numerics) for i in range(k)]
+
+
+def snapshot(odp, features=True):
+    """Everything a caller can observe of a loaded provider."""
+    pos, fid = odp.getPositions()
+    s = {"n": odp.num_epochs(), "pos": pos.tolist(), "fid": fid.tolist(),
+         "labels": odp.getDataLabels(), "error": odp.last_error, "epochs": odp.getData(),
+         "epochs_f32": odp.getData(np.float32)}
+    if features:
+        s["features"] = odp.getFeatures()
+    return s
+
+
+def load(args, k=None, numerics="exact", features=True):
+    """k=None: the one-context provider; k >= 1: eegfx_odp_create_multi over k contexts.
+    Returns (snapshot, shard descriptions, return code)."""
+    ctxs = make_contexts(k or 1, numerics)
+    odp = (fx.OffLineDataProvider(args, context=ctxs[0]) if k is None
+           else fx.OffLineDataProvider(args, contexts=ctxs))
+    try:
+        rc = fx.lib().eegfx_odp_load_data(odp._h)
+        odp.last_error = fx.lib().eegfx_odp_error(odp._h).decode(errors="replace")
+        snap = snapshot(odp, features)
+        shards = [(v.ctx_index, v.device, v.first, v.count, v.features_numerics)
+                  for v in odp.getShards()]
+    finally:
+        odp.close()
+        for c in ctxs:
+            c.close()
+    return snap, shards, rc
+
+
+def assert_same(multi, single):
+    assert multi["n"] == single["n"] and multi["error"] == single["error"]
+    assert multi["pos"] == single["pos"] and multi["fid"] == single["fid"]
+    assert multi["labels"] == single["labels"]
+    assert eq(multi["epochs"], single["epochs"])
+    assert multi["epochs_f32"].dtype == np.float32
+    assert eq(multi["epochs_f32"], single["epochs_f32"])
+    if "features" in single:
+        assert eq(multi["features"], single["features"])
+
+
+def assert_balanced(shards, n, k):
+    n_dev = fx.device_count()
+    assert [(s[0], s[1]) for s in shards] == [(r, r % n_dev) for r in range(k)]
+    assert [(s[2], s[2] + s[3]) for s in shards] == [native_shard_range(n, r, k) for r in range(k)]
+
+
+def test_info_train_three_contexts(golden_vectors):
+    single, one, rc1 = load([INFO_TRAIN])
+    multi, shards, rc = load([INFO_TRAIN], 3)
+    assert rc == rc1 == _lib.EEGFX_OK and multi["error"] == ""
+    assert_same(multi, single)
+    assert_balanced(shards, 11, 3)
+    assert [s[4] for s in shards] == [_lib.EXACT] * 3 and [s[3] for s in one] == [11]
+    g = golden_vectors["infoTrain"]
+    assert multi["pos"] == g["positions"] and multi["labels"] == g["labels"]
+    assert eq(multi["features"], hexrows(g["features_hex"]))
+    assert oracle.java_epoch_sum(multi["epochs"]) == EPOCH_SUM_GOLDEN
+    assert oracle.java_feature_sum(multi["features"]) == FEATURE_SUM_GOLDEN
+
+
+def oracle_rows_per_file(snap, bases):
+    """The oracle's process_recording on each file's own positions, in list order."""
+    rows = []
+    for f, base in enumerate(bases):
+        raw = fx.read_raw(base + ".vhdr", base + ".eeg")
+        pos = [p for p, i in zip(snap["pos"], snap["fid"]) if i == f]
+        rows.append(oracle.process_recording(raw, [0, 1, 2], [0.1] * 3, pos))
+    return np.concatenate(rows)
+
+
+def test_dod02_four_contexts(golden_vectors):
+    args = [DOD02 + ".eeg", "4"]
+    single, _, _ = load(args)
+    multi, shards, rc = load(args, 4)
+    assert rc == _lib.EEGFX_OK
+    assert_same(multi, single)
+    assert_balanced(shards, 27, 4)
+    assert [s[3] for s in shards] == [7, 7, 7, 6]
+    assert eq(multi["features"], oracle_rows_per_file(multi, [DOD02]))
+    assert eq(multi["features"], hexrows(golden_vectors["DoD_2015_02_g4"]["features_hex"]))
+
+
+def test_two_files_five_contexts(tmp_path):
+    info = two_file_info(tmp_path)
+    single, _, _ = load([info])
+    multi, shards, rc = load([info], 5)
+    assert rc == _lib.EEGFX_OK and set(multi["fid"]) == {0, 1}
+    assert_same(multi, single)
+    assert_balanced(shards, multi["n"], 5)
+    assert eq(multi["features"], oracle_rows_per_file(multi, [DOD01, DOD02]))
+    oep, olab, opos, _ = oracle.data_provider([info])
+    assert eq(multi["epochs"], oep) and multi["pos"] == opos and multi["labels"] == olab
+
+
+@pytest.fixture(scope="module")
+def synthetic(tmp_path_factory):
+    info = synthetic_directory(tmp_path_factory.mktemp("odp_multi"))
+    single, _, rc = load([info])
+    assert rc == _lib.EEGFX_OK and single["n"] == 35
+    # the corners are really there: a NaN row (pos - 100 == n_frames) in file 0 and in file 5,
+    # zero-padded tails, nothing from the rejected file (4) or the missing one (1)
+    assert sorted(set(single["fid"])) == [0, 2, 3, 5]
+    nan_rows = np.flatnonzero(np.isnan(single["features"]).all(axis=1)).tolist()
+    assert nan_rows == [5, 34] and single["pos"][5] == 3100 and single["pos"][34] == 6100
+    assert np.all(single["epochs"][4][:, 300:] == single["epochs"][4][:, 300:301])  # padded tail
+    return info, single
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 5, 8])
+def test_synthetic_directory(synthetic, k):
+    info, single = synthetic
+    multi, shards, rc = load([info], k)
+    assert rc == _lib.EEGFX_OK and multi["error"] == ""
+    assert_same(multi, single)
+    assert_balanced(shards, 35, k)
+    if k == 8:
+        files = [single["fid"][s[2]:s[2] + s[3]] for s in shards]
+        assert files[1].count(0) == 1            # one epoch of a file, and its span is empty
+        assert sum(5 in f for f in files) == 3   # a file over three shards
+
+
+def test_other_feature_parameters(synthetic):
+    info, _ = synthetic
+    got = []
+    for k in (None, 3):
+        ctxs = make_contexts(k or 1)
+        odp = (fx.OffLineDataProvider([info], context=ctxs[0]) if k is None
+               else fx.OffLineDataProvider([info], contexts=ctxs))
+        odp.loadData()
+        got.append((odp.getFeatures(skip=100, feature_size=64), odp.getFeatures(feature_size=512),
+                    odp.getFeatures(skip=238), odp.getFeatures(feature_size=5)))
+        odp.close()
+        for c in ctxs:
+            c.close()
+    assert got[0][0].shape == (35, 192) and got[0][1].shape == (35, 1536)
+    for a, b in zip(*got):
+        assert a.shape == b.shape and eq(a, b)
+
+
+@pytest.mark.parametrize("field", ["stimulus", "position"])
+def test_malformed_marker_in_the_second_of_three_files(tmp_path, field):
+    """stimulus: an overflowing stimulus number stops eegfx_plan_markers -- the accepted prefix of
+    that file stays; position: the marker file does not parse -- nothing of that file stays."""
+    info = synthetic_directory(tmp_path)
+    (tmp_path / "syn_info.txt").write_text("syn/a_int16.eeg 1\nsyn/b_float.eeg 1\nsyn/e_tail.eeg 1\n")
+    vmrk = tmp_path / "syn" / "b_float.vmrk"
+    lines = vmrk.read_text(encoding="utf-8").splitlines(keepends=True)
+    bad = [i for i, l in enumerate(lines) if l.startswith("Mk5=")][0]
+    lines[bad] = ("Mk5=Stimulus,S 99999999999,1500,1,0\n" if field == "stimulus"
+                  else "Mk5=Stimulus,S  1,15x0,1,0\n")
+    vmrk.write_text("".join(lines), encoding="utf-8")
+    single, _, rc1 = load([info])
+    multi, shards, rc = load([info], 3)
+    assert rc == rc1 == _lib.EEGFX_EFORMAT and multi["error"] == single["error"] != ""
+    assert multi["n"] == (9 if field == "stimulus" else 6)
+    assert_same(multi, single)
+    assert_balanced(shards, multi["n"], 3)
+
+
+@pytest.mark.parametrize("later_planning_error", [False, True])
+def test_unreadable_payload_found_by_a_worker(tmp_path, later_planning_error):
+    """The second file's .eeg exists but cannot be opened: the one-context provider stops there
+    with EEGFX_EIO and keeps the first file.  Planning does not open payloads, so on the multi
+    provider a worker meets the failure; it overrides an error planning found in a later file, and
+    the shard ranges are the planned ones clipped to what is kept.  (A user who may open any file
+    sees no failure at all; the two providers are still compared.)"""
+    import os
+    info = synthetic_directory(tmp_path)
+    (tmp_path / "syn_info.txt").write_text("syn/a_int16.eeg 1\nsyn/b_float.eeg 1\nsyn/e_tail.eeg 1\n")
+    if later_planning_error:
+        vmrk = tmp_path / "syn" / "e_tail.vmrk"
+        vmrk.write_text(vmrk.read_text(encoding="utf-8") + "Mk99=Stimulus,S  1,15x0,1,0\n",
+                        encoding="utf-8")
+    eeg = str(tmp_path / "syn" / "b_float.eeg")
+    os.chmod(eeg, 0)
+    try:
+        unreadable = not os.access(eeg, os.R_OK)
+        single, _, rc1 = load([info])
+        multi, shards, rc = load([info], 3)
+    finally:
+        os.chmod(eeg, 0o644)
+    assert rc == rc1 and multi["error"] == single["error"]
+    assert_same(multi, single)
+    if unreadable:
+        assert rc == _lib.EEGFX_EIO and "cannot open" in multi["error"] and multi["n"] == 6
+        planned = 15 if later_planning_error else 27     # 6 + 9 (+ 12 where e_tail parses)
+        assert [(s[2], s[3]) for s in shards] == [
+            (min(a, 6), min(b, 6) - min(a, 6))
+            for a, b in (native_shard_range(planned, r, 3) for r in range(3))]
+
+
+def test_fma_rows_within_the_contract(synthetic):
+    info, exact = synthetic
+    fma, shards, rc = load([info], 3, numerics="fma")
+    assert rc == _lib.EEGFX_OK and [s[4] for s in shards] == [_lib.FMA] * 3
+    assert fma["pos"] == exact["pos"] and fma["labels"] == exact["labels"]
+    assert eq(fma["epochs"], exact["epochs"])      # the cut is the same under both numerics
+    nan = np.isnan(exact["features"])
+    assert np.array_equal(np.isnan(fma["features"]), nan)
+    assert np.max(np.abs(fma["features"][~nan] - exact["features"][~nan])) <= FMA_TOL
+
+
+def test_mixed_numerics_and_repeated_context():
+    a, b = fx.Context(0), fx.Context(0, numerics="fma")
+    try:
+        odp = fx.OffLineDataProvider([INFO_TRAIN], contexts=[a, b])
+        assert fx.lib().eegfx_odp_load_data(odp._h) == _lib.EEGFX_EINVAL
+        assert b"numerics" in fx.lib().eegfx_odp_error(odp._h)
+        assert odp.num_epochs() == 0 and [v.count for v in odp.getShards()] == [0, 0]
+        b.set_numerics("exact")      # the same provider loads once the contexts agree
+        odp.loadData()
+        assert odp.last_error == "" and odp.num_epochs() == 11
+        odp.close()
+        with pytest.raises(fx.EegfxError) as e:
+            fx.OffLineDataProvider([INFO_TRAIN], contexts=[a, b, a])
+        assert e.value.code == _lib.EEGFX_EINVAL
+    finally:
+        a.close()
+        b.close()
+
+
+@pytest.mark.parametrize("k", [None, 1, 4])
+def test_shard_views(synthetic, k):
+    """The device views of every shard equal the rows the accessors return; for the one-context
+    provider (k=None) this is the device view it did not have."""
+    import torch
+    info, single = synthetic
+    ctxs = make_contexts(k or 1)
+    odp = (fx.OffLineDataProvider([info], context=ctxs[0]) if k is None
+           else fx.OffLineDataProvider([info], contexts=ctxs))
+    odp.loadData()
+    views = odp.getShards()
+    assert len(views) == (k or 1) and sum(v.count for v in views) == 35
+    for v in views:
+        assert v.features_numerics == _lib.EXACT
+        for view, shape in ((v.epochs, (v.count, 3, 750)), (v.features, (v.count, 48))):
+            cai = view.__cuda_array_interface__
+            assert cai["shape"] == shape and cai["typestr"] == "<f8" and cai["version"] == 2
+            assert cai["data"][0] != 0 and view.read_only
+        ep = torch.as_tensor(v.epochs, device="cuda")
+        ft = torch.as_tensor(v.features, device="cuda")
+        assert ep.data_ptr() == v.epochs.__cuda_array_interface__["data"][0]   # no copy
+        assert ft.data_ptr() == v.features.__cuda_array_interface__["data"][0]
+        assert eq(ep.cpu().numpy(), single["epochs"][v.first:v.first + v.count])
+        assert eq(ft.cpu().numpy(), single["features"][v.first:v.first + v.count])
+        del ep, ft
+    if k is not None:   # after a change of numerics the resident rows keep the ones they have
+        ctxs[0].set_numerics("fma")
+        assert odp.getShards()[0].features_numerics == _lib.EXACT
+        ctxs[0].set_numerics("exact")
+    odp.close()
+    for c in ctxs:
+        c.close()
+
+
+def test_views_keep_the_provider_alive():
+    import gc
+    import torch
+    ctxs = make_contexts(2)
+    odp = fx.OffLineDataProvider([INFO_TRAIN], contexts=ctxs)
+    odp.loadData()
+    want = odp.getData()
+    views = odp.getShards()
+    del odp
+    gc.collect()
+    got = np.concatenate([torch.as_tensor(v.epochs, device="cuda").cpu().numpy() for v in views])
+    assert eq(got, want)
+    views[0].epochs._owner.close()
+    for c in ctxs:
+        c.close()
+
+
+def test_teardown_and_reuse_of_contexts(synthetic):
+    info, single = synthetic
+    ctxs = make_contexts(3)
+    first = fx.OffLineDataProvider([info], contexts=ctxs)
+    first.loadData()
+    first.close()
+    first.close()                      # idempotent
+    second = fx.OffLineDataProvider([info], contexts=ctxs)
+    second.loadData()
+    second.loadData()                  # starts over: the same state, not twice the epochs
+    assert_same(snapshot(second), single)
+    second.close()
+    for c in ctxs:
+        c.close()
+    third_ctxs = make_contexts(3)      # fresh contexts after all of that
+    third = fx.OffLineDataProvider([INFO_TRAIN], contexts=third_ctxs)
+    third.loadData()
+    assert third.num_epochs() == 11
+    third.close()
+    for c in third_ctxs:
+        c.close()

@@ -1,0 +1,183 @@
+"""The OffLineDataProvider over several contexts, host side only: the planning-only provider of
+eegfx_odp_create_multi (ctxs == NULL) reports the shard ranges a device run will use, with the
+same selection as the one-context planning provider; eegfx_shard_span; the argument checks.
+No GPU is touched."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import eeg_dataanalysispackage_amd as fx
+from eeg_dataanalysispackage_amd import _lib
+from eeg_dataanalysispackage_amd.sharding import native_shard_range, shard_span
+from conftest import DOD02, INFO_TRAIN
+from odp_multi_data import synthetic_directory, two_file_info
+
+
+def plan(args, shards=None):
+    odp = fx.OffLineDataProvider(args, plan_only=True, shards=shards)
+    odp.loadData()
+    pos, fid = odp.getPositions()
+    state = (odp.num_epochs(), pos.tolist(), fid.tolist(), odp.getDataLabels(), odp.last_error)
+    views = odp.getShards()
+    odp.close()
+    return state, views
+
+
+def check_plan_views(views, n, k):
+    assert len(views) == k
+    assert [(v.first, v.count) for v in views] == [
+        (s, e - s) for s, e in (native_shard_range(n, r, k) for r in range(k))]
+    assert [v.ctx_index for v in views] == list(range(k))
+    for v in views:
+        assert v.device == -1 and v.features_numerics == -1
+        for view in (v.epochs, v.features):
+            cai = view.__cuda_array_interface__
+            assert cai["data"] == (0, False) and cai["shape"][0] == 0
+            assert cai["typestr"] == "<f8" and cai["version"] == 2
+
+
+def test_info_train_three_shards(golden_vectors):
+    single, one = plan([INFO_TRAIN])
+    multi, views = plan([INFO_TRAIN], shards=3)
+    assert multi == single
+    assert multi[0] == 11 and multi[1] == golden_vectors["infoTrain"]["positions"]
+    assert [(v.first, v.count) for v in views] == [(0, 4), (4, 4), (8, 3)]
+    check_plan_views(views, 11, 3)
+    # the one-context provider is one shard over everything it holds
+    assert [(v.ctx_index, v.device, v.first, v.count) for v in one] == [(0, -1, 0, 11)]
+
+
+def test_dod02_four_shards():
+    single, _ = plan([DOD02 + ".eeg", "4"])
+    multi, views = plan([DOD02 + ".eeg", "4"], shards=4)
+    assert multi == single and multi[0] == 27
+    assert [v.count for v in views] == [7, 7, 7, 6]
+    check_plan_views(views, 27, 4)
+
+
+def test_more_shards_than_epochs():
+    multi, views = plan([INFO_TRAIN], shards=16)
+    assert multi[0] == 11
+    assert sum(v.count == 0 for v in views) == 5
+    firsts = [v.first for v in views]
+    assert firsts == sorted(firsts) and firsts[-1] == 11
+    check_plan_views(views, 11, 16)
+
+
+def test_balance_carries_across_files(tmp_path):
+    info = two_file_info(tmp_path)
+    single, _ = plan([info])
+    multi, views = plan([info], shards=5)
+    assert multi == single and multi[4] == ""
+    n, fid = multi[0], multi[2]
+    assert set(fid) == {0, 1} and fid == sorted(fid)
+    # the second file alone (balance 0 at its start) selects differently: the balance carried
+    alone, _ = plan([str(tmp_path / "DoD" / "DoD_2015_02.eeg"), "4"])
+    second = [p for p, f in zip(multi[1], fid) if f == 1]
+    assert second != alone[1]
+    covered = [i for v in views for i in range(v.first, v.first + v.count)]
+    assert covered == list(range(n))
+    check_plan_views(views, n, 5)
+
+
+def test_synthetic_directory_plan(tmp_path):
+    """The directory of tests/test_gpu_odp_multi.py: 35 epochs, none from the rejected file (index
+    4) or the missing one (index 1); 8 shards leave one shard a single epoch of file 0 and spread
+    file 5 over three shards."""
+    info = synthetic_directory(tmp_path)
+    single, _ = plan([info])
+    multi, views = plan([info], shards=8)
+    assert multi == single and multi[0] == 35 and multi[4] == ""
+    fid = multi[2]
+    assert [fid.count(f) for f in range(6)] == [6, 0, 9, 8, 0, 12]
+    per_shard = [fid[v.first:v.first + v.count] for v in views]
+    assert per_shard[1].count(0) == 1 and multi[1][5] == 3100   # pos - 100 == n_frames, alone
+    assert sum(5 in files for files in per_shard) == 3
+
+
+def span_formula(pos, n_frames):
+    if not len(pos):
+        return 0, 0
+    first = min(pos) - 100
+    return first, min(n_frames, max(pos) + 750) - first
+
+
+@pytest.mark.parametrize("pos,n_frames", [
+    ([5000, 300, 1200, 4100], 20000),   # unsorted
+    ([777], 20000),                      # one position
+    ([400, 19800, 2000], 20000),         # max(pos) + 750 > n_frames: clipped to the end
+    ([20100], 20000),                    # pos - 100 == n_frames: an empty span
+    ([20100, 19000], 20000),
+    ([100], 0),                          # a recording without frames
+    ([], 20000),                         # n == 0
+])
+def test_shard_span(pos, n_frames):
+    assert shard_span(pos, n_frames) == span_formula(pos, n_frames)
+    if pos == [20100]:
+        assert shard_span(pos, n_frames) == (20000, 0)
+    if pos == [400, 19800, 2000]:
+        assert shard_span(pos, n_frames) == (300, 19700)
+
+
+def test_shard_span_refuses_positions_the_plan_never_selects():
+    for pos in ([99], [20101]):
+        with pytest.raises(IndexError):
+            shard_span(pos, 20000)
+
+
+def test_argument_checks():
+    lib = fx.lib()
+    argv = (ctypes.c_char_p * 1)(INFO_TRAIN.encode())
+    h = ctypes.c_void_p()
+    for n_ctx in (0, 65, -1):
+        assert lib.eegfx_odp_create_multi(None, n_ctx, argv, 1, ctypes.byref(h)) == _lib.EEGFX_EINVAL
+        assert h.value is None
+    assert lib.eegfx_odp_create_multi(None, 64, argv, 1, ctypes.byref(h)) == _lib.EEGFX_OK
+    try:
+        assert lib.eegfx_odp_num_shards(h) == 64
+        s = _lib.OdpShard()
+        for i in (-1, 64):
+            assert lib.eegfx_odp_get_shard(h, i, ctypes.byref(s)) == _lib.EEGFX_EINVAL
+        assert lib.eegfx_odp_get_shard(h, 63, ctypes.byref(s)) == _lib.EEGFX_OK
+        assert lib.eegfx_odp_get_shard(h, 0, None) == _lib.EEGFX_EINVAL
+    finally:
+        lib.eegfx_odp_destroy(h)
+    # the one-context planning provider: one shard, index 1 is out of range
+    h1 = ctypes.c_void_p()
+    assert lib.eegfx_odp_create(None, argv, 1, ctypes.byref(h1)) == _lib.EEGFX_OK
+    try:
+        assert lib.eegfx_odp_num_shards(h1) == 1
+        assert lib.eegfx_odp_get_shard(h1, 1, ctypes.byref(_lib.OdpShard())) == _lib.EEGFX_EINVAL
+    finally:
+        lib.eegfx_odp_destroy(h1)
+    with pytest.raises(fx.EegfxError):
+        fx.OffLineDataProvider([INFO_TRAIN], plan_only=True, shards=0)
+    with pytest.raises(ValueError):
+        fx.OffLineDataProvider([INFO_TRAIN], plan_only=True, contexts=[])
+
+
+def test_planning_provider_holds_no_epochs_and_reloads():
+    odp = fx.OffLineDataProvider([INFO_TRAIN], plan_only=True, shards=2)
+    odp.loadData()
+    odp.loadData()          # a multi provider's loadData starts over
+    assert odp.num_epochs() == 11
+    with pytest.raises(fx.EegfxError):
+        odp.getData()
+    odp.close()
+    assert odp.getShards() == []
+
+
+def test_planning_error_keeps_the_prefix(tmp_path):
+    """A malformed stimulus number stops planning in its file: same code path, text, and kept
+    prefix as the one-context planning provider; the shard ranges partition what is kept."""
+    info = synthetic_directory(tmp_path)
+    vmrk = tmp_path / "syn" / "b_float.vmrk"
+    lines = vmrk.read_text(encoding="utf-8").splitlines(keepends=True)
+    bad = [i for i, l in enumerate(lines) if l.startswith("Mk5=")][0]
+    lines[bad] = "Mk5=Stimulus,S 99999999999,1500,1,0\n"
+    vmrk.write_text("".join(lines), encoding="utf-8")
+    single, _ = plan([info])
+    multi, views = plan([info], shards=3)
+    assert multi == single and multi[4] != "" and 6 < multi[0] < 35
+    check_plan_views(views, multi[0], 3)
