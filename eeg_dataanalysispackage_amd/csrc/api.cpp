@@ -1,10 +1,5 @@
-// api.cpp -- eegfx C ABI: device context, compute entry points and the OffLineDataProvider.
-//
-// The data provider mirrors DataTransformation/OffLineDataProvider.java (constructor :78,
-// loadData :88-98, handleInput :111-141, processEEGFiles :147-268, loadFilesFromInfoTxt
-// :283-319, setFileNames :327-365, getData :370, getDataLabels :377) with local files in place
-// of HDFS.  Epochs are cut and baseline-corrected on the GPU and stay resident in HBM; getData()
-// copies them back on demand.
+// api.cpp -- eegfx C ABI: device context and compute entry points.  The context's definition and
+// the helpers shared with the OffLineDataProvider (odp.cpp) are declared in ctx.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,16 +27,8 @@
 
 using namespace eegfx;
 
-#define HIP_CHECK(expr)                                                                 \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) fail(EEGFX_EHIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-  } while (0)
+#include "ctx.h"
 
-// Microseconds a small call's waiter spins before it sleeps (A/B builds vary it).
-#ifndef EEGFX_SMALL_SPIN_US
-#define EEGFX_SMALL_SPIN_US 30
-#endif
 // A/B only: the small-call admission gate around the launch alone (the wait outside it)
 #ifndef EEGFX_GATE_LAUNCH_ONLY
 #define EEGFX_GATE_LAUNCH_ONLY 0
@@ -50,111 +37,13 @@ using namespace eegfx;
 #ifndef EEGFX_STREAM_POS_AFTER
 #define EEGFX_STREAM_POS_AFTER 0
 #endif
-// A/B only: a small call's waiter past the spin polls its event between 10-us sleeps instead of
-// sleeping in the runtime's blocking-sync wait
-#ifndef EEGFX_SMALL_SLEEP_POLL
-#define EEGFX_SMALL_SLEEP_POLL 0
-#endif
 
-namespace {
+namespace eegfx {
 
-// Grow-only device allocation owned by a context, stream-ordered on the context's stream (`*sp`):
-// every use of the buffer is enqueued there (the streamed path's side streams are drained before
-// its call returns), so the old allocation is released behind the work already queued and the new
-// one is ready for the work that follows.  Growing never waits for the device -- other contexts
-// keep running (a hipDeviceSynchronize + hipFree here stalled every context on the device).
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  const hipStream_t* sp = nullptr;
-  void* get(size_t bytes) {
-    if (bytes > cap) {
-      if (p) (void)hipFreeAsync(p, *sp);
-      p = nullptr;
-      cap = 0;
-      if (hipMallocAsync(&p, bytes ? bytes : 1, *sp) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        fail(EEGFX_ENOMEM, "hipMallocAsync(%zu) failed", bytes);
-      }
-      cap = bytes;
-    }
-    return p;
-  }
-  void release() {
-    if (p) (void)hipFreeAsync(p, *sp);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-// Pinned host memory is never returned to the runtime while the process runs: hipHostFree (like
-// hipFree) synchronises the whole device, which waits for every resident per-epoch server of
-// every context (up to its 1 s idle exit) -- a context destroyed or a staging buffer grown on one
-// executor thread stalled every other thread's calls for a second (profiles/r06/dropin_threads).
-// Buffers go back to this process-wide pool instead and are reused by the next request of at
-// least their size with the same flags; the pool holds at most the peak of what was in use.
-struct PinnedPool {
-  std::mutex mu;
-  std::multimap<std::pair<unsigned, size_t>, void*> free;  // (flags, capacity) -> buffer
-  void* take(size_t bytes, unsigned flags, size_t* cap) {
-    bytes = std::max<size_t>(bytes, 64);
-    {
-      std::lock_guard<std::mutex> l(mu);
-      auto it = free.lower_bound({flags, bytes});
-      if (it != free.end() && it->first.first == flags && it->first.second <= 2 * bytes + 65536) {
-        void* p = it->second;
-        *cap = it->first.second;
-        free.erase(it);
-        return p;
-      }
-    }
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes, flags) != hipSuccess) {
-      (void)hipGetLastError();
-      fail(EEGFX_ENOMEM, "hipHostMalloc(%zu) failed", bytes);
-    }
-    *cap = bytes;
-    return p;
-  }
-  void give(void* p, size_t cap, unsigned flags) {
-    if (!p) return;
-    std::lock_guard<std::mutex> l(mu);
-    free.emplace(std::make_pair(flags, cap), p);
-  }
-};
 PinnedPool& pinned_pool() {
   static PinnedPool* pool = new PinnedPool();  // never destroyed: buffers live to process exit
   return *pool;
 }
-
-// Grow-only pinned host buffer (hipHostMalloc: mapped into the device address space, from
-// pinned_pool), for the small-batch IFeatureExtraction path and the streamed path's host staging.
-// Only touched by the owning context's calls, which synchronise before they return.
-struct PinBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  void* get(size_t bytes) {
-    if (bytes > cap) {
-      pinned_pool().give(p, cap, hipHostMallocMapped);
-      p = nullptr;
-      cap = 0;
-      p = pinned_pool().take(bytes, hipHostMallocMapped, &cap);
-    }
-    return p;
-  }
-  void* device_ptr() const {
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess)
-      fail(EEGFX_EHIP, "hipHostGetDevicePointer failed");
-    return d;
-  }
-  void release() {
-    pinned_pool().give(p, cap, hipHostMallocMapped);
-    p = nullptr;
-    cap = 0;
-  }
-};
 
 ChanSel make_sel(const int32_t* cols, const float* res, int C, int ct) {
   if (C < 1 || C > kMaxChannels) fail(EEGFX_EINVAL, "C=%d outside [1, %d]", C, kMaxChannels);
@@ -197,274 +86,7 @@ void check_fe_params(int C, int name, int epoch_size, int skip, int feature_size
 // the resident server (mailbox_request packs nfeat - 1 into 5 bits).
 bool wide_features(int feature_size) { return feature_size > EEGFX_DWT8_FEATURE_SIZE; }
 
-}  // namespace
-
-struct eegfx_ctx {
-  int device = 0;
-  hipStream_t own = nullptr;
-  hipStream_t stream = nullptr;
-  int numerics = EEGFX_EXACT;
-  // Error word of the device-side position checks (fused.hip position_ok): host-mapped pinned
-  // memory the kernels store 1 into; eegfx_ctx_synchronize reports and clears it.
-  int* err_host = nullptr;
-  int* err_dev = nullptr;
-  size_t err_cap = 0;  // pinned_pool capacity of err_host
-  // the fma window kernel's guard strategy (guard.h EEGFX_TRACK_X), set by baseline_kernel in the
-  // same host-mapped block, 8 bytes past the error word
-  unsigned int* track_host() const { return (unsigned int*)((char*)err_host + 8); }
-  unsigned int* track_dev() const { return (unsigned int*)((char*)err_dev + 8); }
-  bool guard_track() const {
-    return EEGFX_TRACK_X == 2 ||
-           (EEGFX_TRACK_X == 1 && __atomic_load_n(track_host(), __ATOMIC_RELAXED) != 0);
-  }
-  bool timing = false;
-  // HIP event pairs bracketing each timed (dominant) kernel launch on the context stream, plus
-  // the algorithmic bytes each launch moved; summed by eegfx_ctx_kernel_stats.
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  std::vector<int64_t> event_bytes;
-  size_t n_timed = 0;
-  DevBuf raw, pos, out, scratch, fused;
-  DevBuf lr_x, lr_y, lr_state, lr_part, lr_mask;  // logistic regression (eegfx_logreg_*)
-  PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
-  PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
-                                         // a sharded provider's worker: the file spans it reads
-  // The fma numerics' conditioning guard (guard.h): device memory holding the flagged-row count
-  // of the current window_wide_kernel launch (first 128 B), then the running totals of recomputed
-  // rows and of rows that went to the second stage, each spread over kGuardSlots lines; the
-  // flagged-row list; guard_checked counts the rows that went through a guarded launch.
-  static constexpr size_t kGuardDevBytes = 128 + 2 * kGuardSlotBytes + 128;  // + Guard::adapt
-  int* guard_dev = nullptr;
-  DevBuf guard_list;
-  int64_t guard_checked = 0;
-  unsigned long long* guard_recomputed_slots() const {
-    return (unsigned long long*)((char*)guard_dev + 128);
-  }
-  unsigned long long* guard_rechecked_slots() const {
-    return (unsigned long long*)((char*)guard_dev + 128 + kGuardSlotBytes);
-  }
-  unsigned long long* guard_adapt() const {
-    return (unsigned long long*)((char*)guard_dev + 128 + 2 * kGuardSlotBytes);
-  }
-  Guard guard_for(int64_t n) {
-    if (numerics == EEGFX_EXACT) return Guard{nullptr, nullptr, nullptr};
-    guard_checked += n;
-    return Guard{guard_dev, (int64_t*)guard_list.get(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1)),
-                 guard_recomputed_slots(), guard_rechecked_slots(), guard_adapt(), track_dev()};
-  }
-  void bind_buffers() {
-    for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list})
-      b->sp = &stream;
-  }
-  void release_buffers() {
-    for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list})
-      b->release();
-    pin_in.release();
-    pin_out.release();
-    pin_chunk[0].release();
-    pin_chunk[1].release();
-  }
-  // streamed path (eegfx_process_recording_streamed): upload / download streams and the chunk
-  // events, created on first use and kept for the context's lifetime
-  hipStream_t up = nullptr, down = nullptr;
-  std::vector<hipEvent_t> copied, done;  // per device chunk buffer: uploaded / kernels done
-  void stream_resources(size_t ring) {
-    if (!up) {
-      HIP_CHECK(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
-      HIP_CHECK(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
-    }
-    while (copied.size() < ring) {
-      hipEvent_t a = nullptr, b = nullptr;
-      HIP_CHECK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-      if (hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        fail(EEGFX_EHIP, "hipEventCreateWithFlags");
-      }
-      copied.push_back(a);
-      done.push_back(b);
-    }
-  }
-  // Completion of a small (latency-bound) call: spinning on an event query returns ~0.5 us sooner
-  // than hipStreamSynchronize (the drop-in bench's launch floor: 11.6 vs 12.2 us).  Past kSmallSpin
-  // the thread sleeps until the event completes (a blocking-sync event: interrupt-driven), so a
-  // waiter is not runnable: with more calling threads than cores (Spark local[*] on a CPU quota),
-  // runnable waiters kept threads whose work had completed off the cores for scheduler slices
-  // (profiles/r06/dropin_gate_ab.log).
-  static constexpr auto kSmallSpin = std::chrono::microseconds(EEGFX_SMALL_SPIN_US);
-  hipEvent_t small_done = nullptr;
-  void record_small() {
-    if (!small_done)
-      HIP_CHECK(hipEventCreateWithFlags(&small_done, hipEventDisableTiming | hipEventBlockingSync));
-    HIP_CHECK(hipEventRecord(small_done, stream));
-  }
-  void wait_small(bool recorded = false) {
-    if (!recorded) record_small();
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e;
-    while ((e = hipEventQuery(small_done)) == hipErrorNotReady) {
-      if (std::chrono::steady_clock::now() - t0 > kSmallSpin) {
-#if EEGFX_SMALL_SLEEP_POLL
-        while ((e = hipEventQuery(small_done)) == hipErrorNotReady)
-          std::this_thread::sleep_for(std::chrono::microseconds(10));
-        break;
-#else
-        HIP_CHECK(hipEventSynchronize(small_done));
-        return;
-#endif
-      }
-    }
-    HIP_CHECK(e);
-  }
-  // The opt-in resident small-batch server (eegfx_ctx_set_mailbox, features_mailbox_kernel): a
-  // host-mapped command block, the kernel's own stream (never the context stream: the kernel
-  // stays resident), the request sequence and the time of the last request.  A server needs a
-  // hardware queue of its own (a queue runs its packets in order: a second kernel behind a
-  // resident one waits for it to idle out), and the highest-priority pool has kMbSlotsPerDevice of
-  // them, so at most that many contexts of the process hold a server slot on a device
-  // (mb_acquire); the others serve their calls on the launch path, and take a slot when one frees.
-  bool mailbox = false;   // enabled by the caller
-  bool mb_slot = false;   // holds one of the device's server slots
-  hipStream_t mb_stream = nullptr;
-  MailboxCmd* mb_host = nullptr;
-  MailboxCmd* mb_dev = nullptr;
-  size_t mb_cap = 0;  // pinned_pool capacity of mb_host
-  uint32_t mb_seq = 0;
-  uint32_t mb_gen = 0;      // launch generation (MailboxCmd::alive)
-  bool mb_live = false;     // launched and not stopped by the host (it may still have idled out)
-  bool mb_started = false;  // the live server has published its generation
-  bool mb_stuck = false;    // a server that did not start in time: stopped, not yet returned
-  std::chrono::steady_clock::time_point mb_last{};
-  static constexpr uint64_t kMbIdleTicks = 100000000;  // 1 s of s_memrealtime (100 MHz)
-  void mb_launch() {
-    // the staging a server reads is fixed for its lifetime (growing it stops the server first)
-    mb_host->rows = pin_in.p ? (const double*)pin_in.device_ptr() : nullptr;
-    mb_host->out = pin_out.p ? (double*)pin_out.device_ptr() : nullptr;
-    if (++mb_gen == 0) mb_gen = 1;
-    HIP_CHECK(launch_features_mailbox(mb_stream, mb_dev, kMbIdleTicks, mb_gen));
-    mb_live = true;
-    mb_started = false;
-  }
-  // Stops a live server: `stop` is seen within one poll.  A server that has not returned after
-  // 10 s (100 ms if it has not been seen to start: its queue is held by another resident kernel)
-  // keeps `stop` set, so it returns as soon as it runs, and is marked stuck; mb_ready clears
-  // `stop` once it has returned.
-  // Returns whether the kernel has returned.
-  bool mb_stop() {
-    if (!mb_host || !mb_live) return true;
-    __atomic_store_n(&mb_host->stop, 1u, __ATOMIC_RELEASE);
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t q;
-    while ((q = hipStreamQuery(mb_stream)) == hipErrorNotReady) {
-      if (std::chrono::steady_clock::now() - t0 >
-          (mb_started ? std::chrono::milliseconds(10000) : std::chrono::milliseconds(100))) {
-        mb_live = false;
-        mb_stuck = true;
-        return false;
-      }
-      std::this_thread::yield();
-    }
-    __atomic_store_n(&mb_host->stop, 0u, __ATOMIC_RELEASE);
-    mb_live = false;
-    HIP_CHECK(q);
-    return true;
-  }
-  // hipSuccess: the server kernel has returned; hipErrorNotReady: it is running; anything else
-  // is an error of the stream and is raised
-  bool mb_returned() {
-    const hipError_t q = hipStreamQuery(mb_stream);
-    if (q == hipErrorNotReady) return false;
-    HIP_CHECK(q);
-    return true;
-  }
-  // Whether the resident server takes this call (false: the launch path).  Takes a device slot
-  // and sets the server up on first use; restarts a server that may be near its 1 s idle exit
-  // (no request for 500 ms) so a request never races that exit; posts nothing until the server
-  // has published its generation, and falls back to the launch path (marking the server stuck)
-  // if it has not started within kMbStartWait.
-  static constexpr auto kMbStartWait = std::chrono::milliseconds(20);
-  bool mb_ready();
-  // One request: n epochs of packed window rows in pin_in -> rows in pin_out (after mb_ready).
-  void mb_serve(int64_t n, int C, int nfeat) {
-    MailboxCmd* m = mb_host;
-    if (++mb_seq == 0) mb_seq = 1;  // 0 means "no request" to the kernel
-    const auto now = std::chrono::steady_clock::now();
-    __atomic_store_n(&m->req, mailbox_request(mb_seq, C, nfeat, n), __ATOMIC_RELEASE);
-    for (uint64_t spin = 1;; ++spin) {
-      if (__atomic_load_n(&m->done, __ATOMIC_ACQUIRE) == mb_seq) break;
-      // as wait_small: a waiter past kSmallSpin sleeps between polls instead of staying runnable
-      if ((spin & 63) == 0 && std::chrono::steady_clock::now() - now > kSmallSpin)
-        std::this_thread::sleep_for(std::chrono::microseconds(10));
-      if ((spin & 4095) == 0) {
-        // a server that returned with the request pending (an error, or a stop from another
-        // path): serve it again on the same stream, after that kernel
-        if (mb_returned() && __atomic_load_n(&m->done, __ATOMIC_ACQUIRE) != mb_seq) mb_launch();
-        if (std::chrono::steady_clock::now() - now > std::chrono::seconds(30))
-          fail(EEGFX_EHIP, "mailbox request %u not served within 30 s", mb_seq);
-      }
-      __builtin_ia32_pause();
-    }
-    mb_last = std::chrono::steady_clock::now();
-  }
-  void release_mailbox();
-  void release_stream_resources() {
-    release_mailbox();
-    if (small_done) (void)hipEventDestroy(small_done);
-    small_done = nullptr;
-    for (hipEvent_t e : copied) (void)hipEventDestroy(e);
-    for (hipEvent_t e : done) (void)hipEventDestroy(e);
-    copied.clear();
-    done.clear();
-    if (up) (void)hipStreamDestroy(up);
-    if (down) (void)hipStreamDestroy(down);
-    up = down = nullptr;
-  }
-
-  void activate() const { HIP_CHECK(hipSetDevice(device)); }
-  // Waits for the stream, then reports (and clears) a device-resident marker position that a
-  // kernel enqueued on this context since the last check refused: every API call that
-  // synchronises does this, so an invalid position surfaces at the first synchronising call
-  // after it (at the latest eegfx_ctx_synchronize), never silently.
-  void check_positions_flag() {
-    if (__atomic_exchange_n(err_host, 0, __ATOMIC_ACQ_REL) != 0)
-      fail(EEGFX_ERANGE,
-           "a device-resident marker position lies outside [100, n_frames + 100] "
-           "(OffLineDataProvider.java:220-225: ArrayIndexOutOfBoundsException); the rows of such "
-           "epochs are unspecified");
-  }
-  void drain() {
-    HIP_CHECK(hipStreamSynchronize(stream));
-    check_positions_flag();
-  }
-  void tic() {
-    if (!timing) return;
-    if (n_timed == events.size()) {
-      // timing only (read after the stream drains): no system-scope fence at each record, so
-      // the bracketed kernel's neighbours pay no cache writeback / invalidate for the timing
-      hipEvent_t a, b;
-      HIP_CHECK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-      HIP_CHECK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-      events.emplace_back(a, b);
-      event_bytes.push_back(0);
-    }
-    HIP_CHECK(hipEventRecord(events[n_timed].first, stream));
-  }
-  void toc(int64_t bytes) {
-    if (!timing) return;
-    HIP_CHECK(hipEventRecord(events[n_timed].second, stream));
-    event_bytes[n_timed] = bytes;
-    ++n_timed;
-  }
-  void destroy_events() {
-    for (auto& e : events) {
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
-    events.clear();
-    event_bytes.clear();
-    n_timed = 0;
-  }
-};
+}  // namespace eegfx
 
 namespace {
 
@@ -674,15 +296,6 @@ int available_processors() {
   return n;
 }
 
-// Joins the threads it holds when it goes out of scope (an exception from emplace_back or from a
-// later call leaves no joinable std::thread behind, which would call std::terminate).
-struct Joiner {
-  std::vector<std::thread> th;
-  ~Joiner() {
-    for (auto& t : th)
-      if (t.joinable()) t.join();
-  }
-};
 
 // Host batches up to this many window bytes go through the zero-copy path of
 // eegfx_extract_features_f64 (about 64 epochs of 3 channels).
@@ -735,6 +348,10 @@ void run_features_from_raw(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n_f
   ctx->toc(0);
 }
 
+}  // namespace
+
+namespace eegfx {
+
 // raw -> epochs + features (device pointers): the one-pass kernels when the layout fits them,
 // else the cut pass followed by the batch extract over the rows it wrote.  E: double or float epochs
 // (eegfx_process_recording_epochs / _f32): the same kernels, the same rows in `feat`.
@@ -759,484 +376,11 @@ void run_epochs_and_features(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n
   ctx->toc(0);
 }
 
-}  // namespace
+template void run_epochs_and_features<double>(eegfx_ctx*, const void*, int, int64_t, int,
+                                              const ChanSel&, int, const int64_t*, int64_t, double*,
+                                              double*);
 
-// ================================================================================================
-// OffLineDataProvider
-// ================================================================================================
-struct eegfx_odp {
-  eegfx_ctx* ctx = nullptr;
-  std::vector<std::string> args;
-  std::string error;
-  // Map<String, Integer> files = new LinkedHashMap<>() (:54): insertion order, put() on an
-  // existing key keeps the position and replaces the value.
-  std::vector<std::pair<std::string, int32_t>> files;
-  std::string file_prefix;
-  std::string vhdr_file, vmrk_file, eeg_file;
-  int32_t fz_index = 0, cz_index = 0, pz_index = 0;  // fields: persist across files (:49-51)
-  int64_t balance = 0;                                // numberOfTargets - numberOfNonTargets
-  int64_t epochs_counter = 0;
-  std::vector<double> labels;
-  std::vector<int64_t> positions;
-  std::vector<int32_t> file_of_epoch;
-  void* d_epochs = nullptr;  // double[n][3][750], resident (hipMalloc, grown copy-on-grow)
-  size_t d_epochs_cap = 0;
-  int64_t n_epochs = 0;
-  // dwt-8 rows of the epochs, double[n][48], computed in the same pass as the epochs
-  // (eegfx_process_recording_epochs) under the numerics of the load; getFeatures() with the
-  // reference's parameters (8, 512, 175, 16) under the same numerics is then a copy
-  void* d_features = nullptr;
-  size_t d_features_cap = 0;
-  int features_numerics = -1;  // -1: no resident rows (not all epochs have them)
-
-  // ---- a provider over several contexts (eegfx_odp_create_multi) --------------------------------
-  // `ctx` stays null: the planning pass is the planning-only provider's and also records, per
-  // file, what a shard needs to cut from it; the epochs then live in `shards`, one per context.
-  bool multi = false;
-  std::vector<eegfx_ctx*> ctxs;  // empty: planning-only
-  int32_t n_shards = 1;
-  struct FilePlan {
-    int32_t file_idx;
-    std::string eeg;
-    Header h;
-    int64_t n_frames;
-    int32_t idx[3];  // Fz, Cz, Pz as they stood at this file
-  };
-  std::vector<FilePlan> plans;
-  struct Shard {
-    int64_t first = 0, count = 0;
-    void* d_epochs = nullptr;    // double[count][3][750] on the shard's context, exact size
-    void* d_features = nullptr;  // double[count][48]
-    int numerics = -1;           // numerics of d_features' rows
-  };
-  std::vector<Shard> shards;
-
-  void put_file(const std::string& k, int32_t v) {
-    for (auto& kv : files)
-      if (kv.first == k) {
-        kv.second = v;
-        return;
-      }
-    files.emplace_back(k, v);
-  }
-
-  static bool ends_with_4(const std::string& s, const char* suf) {
-    // fileLocation.substring(fileLocation.length() - 4): StringIndexOutOfBounds below 4 chars.
-    if (s.size() < 4) fail(EEGFX_EINVAL, "String index out of range: %d", (int)s.size() - 4);
-    return s.compare(s.size() - 4, 4, suf) == 0;
-  }
-
-  void handle_input() {  // :111-141
-    if (args.empty() || args.size() > 6)
-      fail(EEGFX_EINVAL,
-           "Please enter the input in one of these formats: 1. <location of info.txt file> "
-           "2. <location of a .eeg file> <guessed number>  *<optional values>");
-    const std::string& loc = args[0];
-    if (ends_with_4(loc, ".eeg")) {
-      file_prefix = "";
-      if (args.size() < 2) fail(EEGFX_EINVAL, "Index 1 out of bounds for length 1");
-      int32_t g;
-      if (!java_parse_int(args[1], &g))
-        fail(EEGFX_EFORMAT, "For input string: \"%s\"", args[1].c_str());
-      put_file(loc, g);
-    } else if (ends_with_4(loc, ".txt")) {
-      const size_t slash = loc.rfind('/');
-      if (slash == std::string::npos) fail(EEGFX_EINVAL, "String index out of range: -1");
-      file_prefix = loc.substr(0, slash) + "/";
-      load_files_from_info_txt(loc);
-    } else {
-      fail(EEGFX_EINVAL,
-           "Please enter the input in one of these formats: 1. <location of info.txt file> "
-           "2. <location of a .eeg file> <target number>  *<optional values>");
-    }
-  }
-
-  void load_files_from_info_txt(const std::string& loc) {  // :283-319
-    FILE* f = fopen(loc.c_str(), "rb");
-    if (!f) fail(EEGFX_EIO, "File %s does not exist", loc.c_str());
-    std::string text;
-    char buf[4096];
-    size_t r;
-    while ((r = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, r);
-    fclose(f);
-    std::vector<std::string> lines;
-    std::string cur;
-    for (size_t i = 0; i < text.size(); ++i) {  // BufferedReader.readLine
-      const char ch = text[i];
-      if (ch == '\n' || ch == '\r') {
-        lines.push_back(cur);
-        cur.clear();
-        if (ch == '\r' && i + 1 < text.size() && text[i + 1] == '\n') ++i;
-      } else {
-        cur.push_back(ch);
-      }
-    }
-    if (!cur.empty()) lines.push_back(cur);
-    for (const std::string& line : lines) {
-      if (line.empty() || line[0] == '#') continue;
-      std::vector<std::string> parts = java_split_space(line);
-      if (parts.size() > 1) {
-        int32_t num;
-        if (!java_parse_int(parts[1], &num))
-          fail(EEGFX_EFORMAT, "Line %s contains an improper number format", line.c_str());
-        put_file(parts[0], num);
-      }
-    }
-  }
-
-  // setFileNames (:327-365): false = the reference's caught IllegalArgumentException (skip file).
-  bool set_file_names(const std::string& loc, std::string* why) {
-    if (loc.size() <= 4) {
-      *why = "Incorrect file name, must be at least longer than 4 characters ";
-      return false;
-    }
-    if (loc.compare(loc.size() - 4, 4, ".eeg") != 0) {
-      *why = "Invalid .eeg file";
-      return false;
-    }
-    const std::string base = loc.substr(0, loc.rfind('.'));
-    const std::string vhdr = base + ".vhdr", vmrk = base + ".vmrk";
-    if (!file_exists(vhdr)) {
-      *why = "No related .vhdr file found for the original .eeg file " + vhdr;
-      return false;
-    }
-    if (!file_exists(vmrk)) {
-      *why = "No related .vmrk file found for the original .eeg file " + vmrk;
-      return false;
-    }
-    if (!file_exists(loc)) {
-      *why = "No related .eeg file found for the original .eeg file " + loc;
-      return false;
-    }
-    vhdr_file = vhdr;
-    vmrk_file = vmrk;
-    eeg_file = loc;
-    return true;
-  }
-
-  // columns and resolutions of Fz, Cz, Pz (1-based channel numbers) in a recording
-  static ChanSel file_sel(const Header& h, const int32_t idx[3]) {
-    int32_t cols[3];
-    float res[3];
-    for (int c = 0; c < 3; ++c) {
-      cols[c] = idx[c] - 1;
-      res[c] = 1.0f;
-      for (const auto& ci : h.channels)
-        if (ci.number == idx[c]) res[c] = (float)ci.resolution;
-    }
-    return make_sel(cols, res, 3, h.info.n_channels);
-  }
-
-  void append_epochs(const Header& h, int64_t n_frames, const void* d_raw,
-                     const std::vector<int64_t>& pos, int32_t file_idx,
-                     const std::vector<double>& lab) {
-    const int64_t k = (int64_t)pos.size();
-    if (k == 0) return;
-    if (!ctx) {  // planning-only provider: selection, labels and offsets without epochs
-      n_epochs += k;
-      positions.insert(positions.end(), pos.begin(), pos.end());
-      labels.insert(labels.end(), lab.begin(), lab.end());
-      file_of_epoch.insert(file_of_epoch.end(), (size_t)k, file_idx);
-      return;
-    }
-    const int ct = h.info.n_channels;
-    const int32_t idx[3] = {fz_index, cz_index, pz_index};
-    const ChanSel sel = file_sel(h, idx);
-    const size_t per = sizeof(double) * 3 * EEGFX_POSTSTIMULUS;
-    // grow the resident epoch buffer (copy-on-grow)
-    const size_t need = per * (size_t)(n_epochs + k);
-    if (need > d_epochs_cap) {
-      size_t cap = std::max(need, d_epochs_cap * 2);
-      void* np = nullptr;
-      HIP_CHECK(hipMallocAsync(&np, cap, ctx->stream));
-      if (n_epochs)
-        HIP_CHECK(hipMemcpyAsync(np, d_epochs, per * (size_t)n_epochs, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-      if (d_epochs) HIP_CHECK(hipFreeAsync(d_epochs, ctx->stream));
-      d_epochs = np;
-      d_epochs_cap = cap;
-    }
-    const size_t fper = sizeof(double) * 3 * EEGFX_DWT8_FEATURE_SIZE;
-    const size_t fneed = fper * (size_t)(n_epochs + k);
-    if (fneed > d_features_cap) {
-      size_t cap = std::max(fneed, d_features_cap * 2);
-      void* np = nullptr;
-      HIP_CHECK(hipMallocAsync(&np, cap, ctx->stream));
-      if (n_epochs && features_numerics >= 0)
-        HIP_CHECK(hipMemcpyAsync(np, d_features, fper * (size_t)n_epochs, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-      if (d_features) HIP_CHECK(hipFreeAsync(d_features, ctx->stream));
-      d_features = np;
-      d_features_cap = cap;
-    }
-    int64_t* d_pos = (int64_t*)ctx->pos.get(sizeof(int64_t) * (size_t)k);
-    HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), sizeof(int64_t) * (size_t)k,
-                             hipMemcpyHostToDevice, ctx->stream));
-    // getData()'s epochs and their dwt-8 rows in one pass over each epoch's frames
-    run_epochs_and_features(ctx, d_raw, h.info.binary_format, n_frames, ct, sel, 3, d_pos, k,
-                            (double*)((char*)d_epochs + per * (size_t)n_epochs),
-                            (double*)((char*)d_features + fper * (size_t)n_epochs));
-    if (n_epochs == 0) features_numerics = ctx->numerics;
-    else if (features_numerics != ctx->numerics) features_numerics = -1;
-    ctx->drain();
-    n_epochs += k;
-    positions.insert(positions.end(), pos.begin(), pos.end());
-    labels.insert(labels.end(), lab.begin(), lab.end());
-    file_of_epoch.insert(file_of_epoch.end(), (size_t)k, file_idx);
-  }
-
-  void process_eeg_files() {  // :147-268
-    int32_t file_idx = -1;
-    for (const auto& entry : files) {
-      ++file_idx;
-      std::string why;
-      if (!set_file_names(file_prefix + entry.first, &why)) continue;  // logged + skipped (:157-161)
-      const Header h = read_header(vhdr_file);
-      for (const auto& ch : h.channels) {  // :172-183
-        std::string name = ch.name;
-        for (auto& c : name) c = (char)tolower((unsigned char)c);
-        if (name == "fz") fz_index = ch.number;
-        else if (name == "cz") cz_index = ch.number;
-        if (name == "pz") pz_index = ch.number;
-      }
-      const int32_t sel[3] = {fz_index, cz_index, pz_index};
-      for (int c = 0; c < 3; ++c)
-        if (sel[c] < 1 || sel[c] > h.info.n_channels)
-          fail(EEGFX_EINVAL, "%s: channel %s not found (index %d)", vhdr_file.c_str(),
-               c == 0 ? "Fz" : c == 1 ? "Cz" : "Pz", sel[c]);
-      const int64_t n_frames = recording_frames(h, eeg_file);
-      if (multi) plans.push_back(FilePlan{file_idx, eeg_file, h, n_frames, {sel[0], sel[1], sel[2]}});
-      const size_t raw_bytes =
-          (size_t)n_frames * h.info.n_channels * sample_bytes(h.info.binary_format);
-      void* d_raw = nullptr;
-      if (ctx) {  // planning-only providers (no context) never touch the recording payload
-        std::vector<char> host(raw_bytes);
-        read_recording(h, eeg_file, host.data(), n_frames);
-        d_raw = ctx->raw.get(raw_bytes);
-        HIP_CHECK(hipMemcpyAsync(d_raw, host.data(), raw_bytes, hipMemcpyHostToDevice,
-                                 ctx->stream));
-      }
-
-      const std::vector<eegfx_marker> markers = read_markers(vmrk_file);
-      std::vector<int64_t> pos(markers.size());
-      std::vector<double> lab(markers.size());
-      int64_t k = 0;
-      const int rc = eegfx_plan_markers(markers.data(), (int64_t)markers.size(), n_frames,
-                                        entry.second, &balance, pos.data(), lab.data(), &k);
-      pos.resize((size_t)k);
-      lab.resize((size_t)k);
-      epochs_counter += k;
-      append_epochs(h, n_frames, d_raw, pos, file_idx, lab);  // epochs accepted before an error
-      if (rc != EEGFX_OK) fail(rc, "%s", last_error().c_str());
-    }
-  }
-
-  // ---- several contexts: plan once on the host, then one worker per context ---------------------
-  void release_shards() {
-    for (size_t r = 0; r < shards.size() && r < ctxs.size(); ++r) {
-      Shard& s = shards[r];
-      if (!s.d_epochs && !s.d_features) continue;
-      (void)hipSetDevice(ctxs[r]->device);
-      if (s.d_epochs) (void)hipFreeAsync(s.d_epochs, ctxs[r]->stream);
-      if (s.d_features) (void)hipFreeAsync(s.d_features, ctxs[r]->stream);
-      (void)hipStreamSynchronize(ctxs[r]->stream);
-      s.d_epochs = s.d_features = nullptr;
-    }
-  }
-
-  // Shard r: eegfx_shard_range(planned, r, n_shards) clipped to the first `kept` epochs.
-  void set_ranges(int64_t planned, int64_t kept) {
-    for (int32_t r = 0; r < n_shards; ++r) {
-      int64_t a = 0, b = 0;
-      if (eegfx_shard_range(planned, r, n_shards, &a, &b) != EEGFX_OK)
-        fail(EEGFX_EINVAL, "%s", last_error().c_str());
-      shards[(size_t)r].first = std::min(a, kept);
-      shards[(size_t)r].count = std::min(b, kept) - std::min(a, kept);
-    }
-  }
-
-  struct WorkerError {
-    int code = EEGFX_OK;
-    int32_t file = -1;  // index (in `files`) of the file the worker was on
-    std::string text;
-  };
-
-  // The worker of context r: the files its range intersects, in order; of each, the frames
-  // eegfx_shard_span names, through two pinned staging buffers (the read of one file overlaps the
-  // upload and the kernels of the one before), into the epochs' slots of the shard's buffers.
-  void run_shard(size_t r, const std::vector<int32_t>& plan_of_file, WorkerError* we) {
-    eegfx_ctx* c = ctxs[r];
-    Shard& s = shards[r];
-    int32_t cur_file = file_of_epoch[(size_t)s.first];
-    struct Events {
-      hipEvent_t e[2] = {nullptr, nullptr};
-      ~Events() {
-        for (hipEvent_t x : e)
-          if (x) (void)hipEventDestroy(x);
-      }
-    } staged;
-    bool used[2] = {false, false};
-    try {
-      c->activate();
-      const size_t per = sizeof(double) * 3 * EEGFX_POSTSTIMULUS;
-      const size_t fper = sizeof(double) * 3 * EEGFX_DWT8_FEATURE_SIZE;
-      HIP_CHECK(hipMallocAsync(&s.d_epochs, per * (size_t)s.count, c->stream));
-      HIP_CHECK(hipMallocAsync(&s.d_features, fper * (size_t)s.count, c->stream));
-      s.numerics = c->numerics;
-      for (hipEvent_t& x : staged.e) HIP_CHECK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-      const int64_t end = s.first + s.count;
-      int b = 0;
-      for (int64_t i = s.first; i < end; b ^= 1) {
-        const int32_t f = file_of_epoch[(size_t)i];
-        cur_file = f;
-        int64_t j = i;
-        while (j < end && file_of_epoch[(size_t)j] == f) ++j;
-        const int64_t k = j - i;
-        const FilePlan& fp = plans[(size_t)plan_of_file[(size_t)f]];
-        int64_t first = 0, frames = 0;
-        if (eegfx_shard_span(&positions[(size_t)i], k, fp.n_frames, &first, &frames) != EEGFX_OK)
-          fail(EEGFX_EINVAL, "%s", last_error().c_str());
-        // pos - 100 == n_frames for every epoch of the span: one frame earlier, so that no kernel
-        // is launched on an empty recording (a recording of no frames at all stays empty, as it
-        // is for the one-context provider)
-        if (frames == 0 && first > 0) {
-          --first;
-          frames = 1;
-        }
-        const int ct = fp.h.info.n_channels;
-        const size_t raw_bytes = (size_t)frames * ct * sample_bytes(fp.h.info.binary_format);
-        const size_t pos_off = (raw_bytes + 7) & ~(size_t)7;
-        if (used[b]) HIP_CHECK(hipEventSynchronize(staged.e[b]));  // its last upload has left it
-        char* host = (char*)c->pin_chunk[b].get(pos_off + sizeof(int64_t) * (size_t)k);
-        read_recording_span(fp.h, fp.eeg, host, fp.n_frames, first, frames);
-        int64_t* h_pos = (int64_t*)(host + pos_off);
-        for (int64_t t = 0; t < k; ++t) h_pos[t] = positions[(size_t)(i + t)] - first;
-        void* d_raw = c->raw.get(raw_bytes);
-        if (raw_bytes)
-          HIP_CHECK(hipMemcpyAsync(d_raw, host, raw_bytes, hipMemcpyHostToDevice, c->stream));
-        int64_t* d_pos = (int64_t*)c->pos.get(sizeof(int64_t) * (size_t)k);
-        HIP_CHECK(hipMemcpyAsync(d_pos, h_pos, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice,
-                                 c->stream));
-        HIP_CHECK(hipEventRecord(staged.e[b], c->stream));
-        used[b] = true;
-        run_epochs_and_features(c, d_raw, fp.h.info.binary_format, frames, ct,
-                                file_sel(fp.h, fp.idx), 3, d_pos, k,
-                                (double*)((char*)s.d_epochs + per * (size_t)(i - s.first)),
-                                (double*)((char*)s.d_features + fper * (size_t)(i - s.first)));
-        i = j;
-      }
-      c->drain();
-    } catch (const Error& e) {
-      *we = WorkerError{e.code, cur_file, e.what()};
-    } catch (const std::bad_alloc&) {
-      *we = WorkerError{EEGFX_ENOMEM, cur_file, "out of host memory"};
-    } catch (const std::exception& e) {
-      *we = WorkerError{EEGFX_EINVAL, cur_file, e.what()};
-    }
-    // after a failure copies may still read the staging buffers: nothing is left in flight
-    if (we->code != EEGFX_OK) (void)hipStreamSynchronize(c->stream);
-  }
-
-  // Runs the workers and joins them; the failure in the earliest file, if any.
-  WorkerError compute() {
-    std::vector<int32_t> plan_of_file(files.size(), -1);
-    for (size_t p = 0; p < plans.size(); ++p) plan_of_file[(size_t)plans[p].file_idx] = (int32_t)p;
-    std::vector<WorkerError> errs(shards.size());
-    {
-      Joiner workers;
-      for (size_t r = 0; r < shards.size(); ++r)
-        if (shards[r].count > 0)
-          workers.th.emplace_back([this, r, &plan_of_file, &errs] {
-            run_shard(r, plan_of_file, &errs[r]);
-          });
-    }
-    WorkerError worst;
-    for (const WorkerError& e : errs)
-      if (e.code != EEGFX_OK && (worst.code == EEGFX_OK || e.file < worst.file)) worst = e;
-    return worst;
-  }
-
-  int load_multi() {
-    int rc = guarded([&] {
-      release_shards();
-      shards.assign((size_t)n_shards, Shard());
-      files.clear();
-      plans.clear();
-      labels.clear();
-      positions.clear();
-      file_of_epoch.clear();
-      file_prefix.clear();
-      n_epochs = epochs_counter = balance = 0;
-      fz_index = cz_index = pz_index = 0;
-      for (size_t r = 1; r < ctxs.size(); ++r)
-        if (ctxs[r]->numerics != ctxs[0]->numerics)
-          fail(EEGFX_EINVAL,
-               "the contexts of a provider must hold the same numerics at loadData (context %d "
-               "holds %d, context 0 holds %d)", (int)r, ctxs[r]->numerics, ctxs[0]->numerics);
-      handle_input();
-      process_eeg_files();  // ctx == nullptr: the planning pass, in file order
-    });
-    std::string text = rc == EEGFX_OK ? "" : last_error();
-    const int64_t planned = n_epochs;
-    const int rc2 = guarded([&] {
-      set_ranges(planned, planned);
-      if (ctxs.empty() || planned == 0) return;
-      WorkerError w;
-      try {
-        w = compute();
-      } catch (const std::exception& e) {  // no worker ran to its end: nothing is kept
-        w = WorkerError{EEGFX_EINVAL, 0, e.what()};
-      }
-      if (w.code == EEGFX_OK) return;
-      // the one-context provider would have stopped in that file: the files before it stay
-      const int64_t kept =
-          std::lower_bound(file_of_epoch.begin(), file_of_epoch.end(), w.file) -
-          file_of_epoch.begin();
-      positions.resize((size_t)kept);
-      labels.resize((size_t)kept);
-      file_of_epoch.resize((size_t)kept);
-      n_epochs = kept;
-      set_ranges(planned, kept);
-      fail(w.code, "%s", w.text.c_str());
-    });
-    if (rc2 != EEGFX_OK) {
-      rc = rc2;
-      text = last_error();
-    }
-    error = text;
-    set_last_error(text);
-    return rc;
-  }
-
-  // An accessor's work on every shard that holds epochs: `enqueue(ctx, shard)` on each context's
-  // stream first, then every context is drained, so the devices work at the same time.  Whatever
-  // was enqueued is drained even when a later step fails (it writes into the caller's buffer).
-  template <typename F>
-  void on_shards(F&& enqueue) const {
-    size_t started = 0;
-    std::unique_ptr<Error> first;
-    try {
-      for (; started < shards.size(); ++started) {
-        if (shards[started].count == 0) continue;
-        ctxs[started]->activate();
-        enqueue(ctxs[started], shards[started]);
-      }
-    } catch (const Error& e) {
-      first.reset(new Error(e));
-      started = std::min(started + 1, shards.size());
-    }
-    for (size_t r = 0; r < started; ++r) {
-      if (shards[r].count == 0) continue;
-      try {
-        ctxs[r]->activate();
-        ctxs[r]->drain();
-      } catch (const Error& e) {
-        if (!first) first.reset(new Error(e));
-      }
-    }
-    if (first) throw *first;
-  }
-};
+}  // namespace eegfx
 
 namespace eegfx {
 int ctx_device(const eegfx_ctx* ctx) { return ctx->device; }
@@ -2174,248 +1318,6 @@ int eegfx_synth_recording(eegfx_ctx* ctx, int16_t* dst, int64_t n_frames, int32_
     ctx->activate();
     HIP_CHECK(launch_synth(ctx->stream, dst, n_frames, n_channels, seed));
   });
-}
-
-// ---- OffLineDataProvider ----------------------------------------------------------------------
-int eegfx_odp_create(eegfx_ctx* ctx, const char* const* args, int32_t n_args, eegfx_odp** out) {
-  return guarded([&] {
-    if (!out || (n_args > 0 && !args) || n_args < 0) fail(EEGFX_EINVAL, "null argument");
-    std::unique_ptr<eegfx_odp> o(new eegfx_odp());
-    o->ctx = ctx;
-    for (int i = 0; i < n_args; ++i) o->args.emplace_back(args[i] ? args[i] : "");
-    *out = o.release();
-  });
-}
-
-int eegfx_odp_load_data(eegfx_odp* odp) {
-  if (!odp) {
-    set_last_error("null provider");
-    return EEGFX_EINVAL;
-  }
-  if (odp->multi) return odp->load_multi();
-  // loadData (:88-98): every exception is logged as fatal and swallowed; what was loaded stays.
-  const int rc = guarded([&] {
-    if (odp->ctx) odp->ctx->activate();
-    odp->handle_input();
-    odp->process_eeg_files();
-  });
-  odp->error = rc == EEGFX_OK ? "" : last_error();
-  return rc;
-}
-
-const char* eegfx_odp_error(const eegfx_odp* odp) { return odp ? odp->error.c_str() : "null provider"; }
-
-int64_t eegfx_odp_num_epochs(const eegfx_odp* odp) { return odp ? odp->n_epochs : 0; }
-
-int eegfx_odp_get_data(const eegfx_odp* odp, double* out) {
-  return guarded([&] {
-    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
-    if (!odp->n_epochs) return;
-    if (odp->multi && !odp->ctxs.empty()) {
-      const size_t per = sizeof(double) * 3 * EEGFX_POSTSTIMULUS;
-      odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
-        HIP_CHECK(hipMemcpyAsync((char*)out + per * (size_t)s.first, s.d_epochs,
-                                 per * (size_t)s.count, hipMemcpyDeviceToHost, ctx->stream));
-      });
-      return;
-    }
-    if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
-    odp->ctx->activate();
-    HIP_CHECK(hipMemcpyAsync(out, odp->d_epochs,
-                             sizeof(double) * 3 * EEGFX_POSTSTIMULUS * (size_t)odp->n_epochs,
-                             hipMemcpyDeviceToHost, odp->ctx->stream));
-    odp->ctx->drain();
-  });
-}
-
-int eegfx_odp_get_data_f32(const eegfx_odp* odp, float* out) {
-  return guarded([&] {
-    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
-    if (!odp->n_epochs) return;
-    if (odp->multi && !odp->ctxs.empty()) {
-      odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
-        const int64_t count = 3 * EEGFX_POSTSTIMULUS * s.count;
-        float* d_f32 = (float*)ctx->scratch.get(sizeof(float) * (size_t)count);
-        HIP_CHECK(launch_narrow_epochs(ctx->stream, (const double*)s.d_epochs, d_f32, count));
-        HIP_CHECK(hipMemcpyAsync(out + 3 * EEGFX_POSTSTIMULUS * s.first, d_f32,
-                                 sizeof(float) * (size_t)count, hipMemcpyDeviceToHost,
-                                 ctx->stream));
-      });
-      return;
-    }
-    if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
-    eegfx_ctx* ctx = odp->ctx;
-    ctx->activate();
-    // the resident epochs stay double; a narrowing kernel feeds the copy (exact: every value is a
-    // widened fp32), so half the bytes cross the host link
-    const int64_t count = 3 * EEGFX_POSTSTIMULUS * (int64_t)odp->n_epochs;
-    float* d_f32 = (float*)ctx->scratch.get(sizeof(float) * (size_t)count);
-    HIP_CHECK(launch_narrow_epochs(ctx->stream, (const double*)odp->d_epochs, d_f32, count));
-    HIP_CHECK(hipMemcpyAsync(out, d_f32, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost,
-                             ctx->stream));
-    ctx->drain();
-  });
-}
-
-int eegfx_odp_get_labels(const eegfx_odp* odp, double* out) {
-  return guarded([&] {
-    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
-    std::copy(odp->labels.begin(), odp->labels.end(), out);
-  });
-}
-
-int eegfx_odp_get_positions(const eegfx_odp* odp, int64_t* pos_out, int32_t* file_out) {
-  return guarded([&] {
-    if (!odp) fail(EEGFX_EINVAL, "null argument");
-    if (pos_out) std::copy(odp->positions.begin(), odp->positions.end(), pos_out);
-    if (file_out) std::copy(odp->file_of_epoch.begin(), odp->file_of_epoch.end(), file_out);
-  });
-}
-
-int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int32_t skip,
-                           int32_t feature_size, double* out) {
-  return guarded([&] {
-    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
-    check_fe_params(3, name, epoch_size, skip, feature_size);
-    if (!odp->n_epochs) return;
-    if (odp->multi && !odp->ctxs.empty()) {
-      const size_t row = sizeof(double) * 3 * (size_t)feature_size;
-      odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
-        char* dst = (char*)out + row * (size_t)s.first;
-        const size_t bytes = row * (size_t)s.count;
-        if (skip == EEGFX_DWT8_SKIP && feature_size == EEGFX_DWT8_FEATURE_SIZE &&
-            s.numerics == ctx->numerics && s.d_features) {
-          HIP_CHECK(hipMemcpyAsync(dst, s.d_features, bytes, hipMemcpyDeviceToHost, ctx->stream));
-          return;
-        }
-        double* d_out = (double*)ctx->out.get(bytes);
-        if (wide_features(feature_size)) {
-          HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)s.d_epochs, s.count, 3,
-                                               skip, feature_size, d_out, EEGFX_POSTSTIMULUS));
-        } else {
-          const Guard g = ctx->guard_for(s.count);
-          HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)s.d_epochs, s.count, 3,
-                                                skip, feature_size, ctx->numerics != EEGFX_EXACT,
-                                                d_out, EEGFX_POSTSTIMULUS, g));
-        }
-        HIP_CHECK(hipMemcpyAsync(dst, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-      });
-      return;
-    }
-    if (!odp->ctx) fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
-    eegfx_ctx* ctx = odp->ctx;
-    ctx->activate();
-    const size_t out_bytes = sizeof(double) * (size_t)odp->n_epochs * 3 * feature_size;
-    if (skip == EEGFX_DWT8_SKIP && feature_size == EEGFX_DWT8_FEATURE_SIZE &&
-        odp->features_numerics == ctx->numerics && odp->d_features) {
-      // the rows computed with the epochs at loadData (the one-pass kernels)
-      HIP_CHECK(hipMemcpyAsync(out, odp->d_features, out_bytes, hipMemcpyDeviceToHost,
-                               ctx->stream));
-      ctx->drain();
-      return;
-    }
-    double* d_out = (double*)ctx->out.get(out_bytes);
-    if (wide_features(feature_size)) {
-      HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)odp->d_epochs,
-                                           odp->n_epochs, 3, skip, feature_size, d_out,
-                                           EEGFX_POSTSTIMULUS));
-    } else {
-      const Guard g = ctx->guard_for(odp->n_epochs);
-      HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)odp->d_epochs,
-                                            odp->n_epochs, 3, skip, feature_size,
-                                            ctx->numerics != EEGFX_EXACT, d_out,
-                                            EEGFX_POSTSTIMULUS, g));
-    }
-    HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->drain();
-  });
-}
-
-int eegfx_odp_create_multi(eegfx_ctx* const* ctxs, int32_t n_ctx, const char* const* args,
-                           int32_t n_args, eegfx_odp** out) {
-  return guarded([&] {
-    if (!out || (n_args > 0 && !args) || n_args < 0) fail(EEGFX_EINVAL, "null argument");
-    if (n_ctx < 1 || n_ctx > EEGFX_ODP_MAX_SHARDS)
-      fail(EEGFX_EINVAL, "%d contexts outside [1, %d]", n_ctx, EEGFX_ODP_MAX_SHARDS);
-    std::unique_ptr<eegfx_odp> o(new eegfx_odp());
-    o->multi = true;
-    o->n_shards = n_ctx;
-    for (int i = 0; ctxs && i < n_ctx; ++i) {
-      if (!ctxs[i]) fail(EEGFX_EINVAL, "context %d is null", i);
-      for (int j = 0; j < i; ++j)
-        if (ctxs[j] == ctxs[i])
-          fail(EEGFX_EINVAL, "context %d repeats context %d: two shards would share its buffers", i,
-               j);
-      o->ctxs.push_back(ctxs[i]);
-    }
-    o->shards.assign((size_t)n_ctx, eegfx_odp::Shard());
-    for (int i = 0; i < n_args; ++i) o->args.emplace_back(args[i] ? args[i] : "");
-    *out = o.release();
-  });
-}
-
-int eegfx_odp_num_shards(const eegfx_odp* odp) { return odp ? odp->n_shards : 0; }
-
-int eegfx_odp_get_shard(const eegfx_odp* odp, int32_t i, eegfx_odp_shard* out) {
-  return guarded([&] {
-    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
-    if (i < 0 || i >= odp->n_shards)
-      fail(EEGFX_EINVAL, "shard %d outside [0, %d)", i, odp->n_shards);
-    eegfx_odp_shard v = {i, -1, 0, 0, nullptr, nullptr, -1};
-    if (odp->multi) {
-      const eegfx_odp::Shard& s = odp->shards[(size_t)i];
-      v.first = s.first;
-      v.count = s.count;
-      if (!odp->ctxs.empty()) {
-        v.device = odp->ctxs[(size_t)i]->device;
-        if (s.count > 0) {
-          v.epochs = (const double*)s.d_epochs;
-          v.features = (const double*)s.d_features;
-          v.features_numerics = s.d_features ? s.numerics : -1;
-        }
-      }
-    } else {
-      v.count = odp->n_epochs;
-      if (odp->ctx) {
-        v.device = odp->ctx->device;
-        if (odp->n_epochs > 0) {
-          v.epochs = (const double*)odp->d_epochs;
-          if (odp->features_numerics >= 0 && odp->d_features) {
-            v.features = (const double*)odp->d_features;
-            v.features_numerics = odp->features_numerics;
-          }
-        }
-      }
-    }
-    *out = v;
-  });
-}
-
-int eegfx_shard_span(const int64_t* pos, int64_t n, int64_t n_frames, int64_t* first_frame,
-                     int64_t* frames) {
-  return guarded([&] {
-    if (n < 0 || n_frames < 0 || (n > 0 && !pos) || !first_frame || !frames)
-      fail(EEGFX_EINVAL, "shard_span(n=%lld, n_frames=%lld)", (long long)n, (long long)n_frames);
-    *first_frame = *frames = 0;
-    if (n == 0) return;
-    const auto mm = std::minmax_element(pos, pos + n);
-    check_positions(mm.first, 1, n_frames);
-    check_positions(mm.second, 1, n_frames);
-    *first_frame = *mm.first - EEGFX_PRESTIMULUS;
-    *frames = std::min(n_frames, *mm.second + EEGFX_POSTSTIMULUS) - *first_frame;
-  });
-}
-
-void eegfx_odp_destroy(eegfx_odp* odp) {
-  if (!odp) return;
-  odp->release_shards();
-  if (odp->ctx && (odp->d_epochs || odp->d_features)) {
-    (void)hipSetDevice(odp->ctx->device);
-    if (odp->d_epochs) (void)hipFreeAsync(odp->d_epochs, odp->ctx->stream);
-    if (odp->d_features) (void)hipFreeAsync(odp->d_features, odp->ctx->stream);
-    (void)hipStreamSynchronize(odp->ctx->stream);
-  }
-  delete odp;
 }
 
 }  // extern "C"

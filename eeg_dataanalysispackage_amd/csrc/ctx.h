@@ -1,0 +1,438 @@
+// ctx.h -- the device context (struct eegfx_ctx) and the helpers that the host sources share:
+// what api.cpp defines and odp.cpp (the OffLineDataProvider) uses.  Internal: not installed.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <map>
+#include <mutex>
+#include <thread>
+#include <utility>
+#include <vector>
+
+#include "common.h"
+#include "eegfx_ext.h"
+#include "launch.h"
+
+
+#define HIP_CHECK(expr)                                                                 \
+  do {                                                                                  \
+    hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess) fail(EEGFX_EHIP, "%s: %s", #expr, hipGetErrorString(_e));     \
+  } while (0)
+
+// Microseconds a small call's waiter spins before it sleeps (A/B builds vary it).
+#ifndef EEGFX_SMALL_SPIN_US
+#define EEGFX_SMALL_SPIN_US 30
+#endif
+// A/B only: a small call's waiter past the spin polls its event between 10-us sleeps instead of
+// sleeping in the runtime's blocking-sync wait
+#ifndef EEGFX_SMALL_SLEEP_POLL
+#define EEGFX_SMALL_SLEEP_POLL 0
+#endif
+
+namespace eegfx {
+
+// Grow-only device allocation owned by a context, stream-ordered on the context's stream (`*sp`):
+// every use of the buffer is enqueued there (the streamed path's side streams are drained before
+// its call returns), so the old allocation is released behind the work already queued and the new
+// one is ready for the work that follows.  Growing never waits for the device -- other contexts
+// keep running (a hipDeviceSynchronize + hipFree here stalled every context on the device).
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  const hipStream_t* sp = nullptr;
+  void* get(size_t bytes) {
+    if (bytes > cap) {
+      if (p) (void)hipFreeAsync(p, *sp);
+      p = nullptr;
+      cap = 0;
+      if (hipMallocAsync(&p, bytes ? bytes : 1, *sp) != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        fail(EEGFX_ENOMEM, "hipMallocAsync(%zu) failed", bytes);
+      }
+      cap = bytes;
+    }
+    return p;
+  }
+  void release() {
+    if (p) (void)hipFreeAsync(p, *sp);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// Pinned host memory is never returned to the runtime while the process runs: hipHostFree (like
+// hipFree) synchronises the whole device, which waits for every resident per-epoch server of
+// every context (up to its 1 s idle exit) -- a context destroyed or a staging buffer grown on one
+// executor thread stalled every other thread's calls for a second (profiles/r06/dropin_threads).
+// Buffers go back to this process-wide pool instead and are reused by the next request of at
+// least their size with the same flags; the pool holds at most the peak of what was in use.
+struct PinnedPool {
+  std::mutex mu;
+  std::multimap<std::pair<unsigned, size_t>, void*> free;  // (flags, capacity) -> buffer
+  void* take(size_t bytes, unsigned flags, size_t* cap) {
+    bytes = std::max<size_t>(bytes, 64);
+    {
+      std::lock_guard<std::mutex> l(mu);
+      auto it = free.lower_bound({flags, bytes});
+      if (it != free.end() && it->first.first == flags && it->first.second <= 2 * bytes + 65536) {
+        void* p = it->second;
+        *cap = it->first.second;
+        free.erase(it);
+        return p;
+      }
+    }
+    void* p = nullptr;
+    if (hipHostMalloc(&p, bytes, flags) != hipSuccess) {
+      (void)hipGetLastError();
+      fail(EEGFX_ENOMEM, "hipHostMalloc(%zu) failed", bytes);
+    }
+    *cap = bytes;
+    return p;
+  }
+  void give(void* p, size_t cap, unsigned flags) {
+    if (!p) return;
+    std::lock_guard<std::mutex> l(mu);
+    free.emplace(std::make_pair(flags, cap), p);
+  }
+};
+PinnedPool& pinned_pool();
+
+// Grow-only pinned host buffer (hipHostMalloc: mapped into the device address space, from
+// pinned_pool), for the small-batch IFeatureExtraction path and the streamed path's host staging.
+// Only touched by the owning context's calls, which synchronise before they return.
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  void* get(size_t bytes) {
+    if (bytes > cap) {
+      pinned_pool().give(p, cap, hipHostMallocMapped);
+      p = nullptr;
+      cap = 0;
+      p = pinned_pool().take(bytes, hipHostMallocMapped, &cap);
+    }
+    return p;
+  }
+  void* device_ptr() const {
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess)
+      fail(EEGFX_EHIP, "hipHostGetDevicePointer failed");
+    return d;
+  }
+  void release() {
+    pinned_pool().give(p, cap, hipHostMallocMapped);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+ChanSel make_sel(const int32_t* cols, const float* res, int C, int ct);
+void check_positions(const int64_t* pos, int64_t n, int64_t n_frames);
+void check_fe_params(int C, int name, int epoch_size, int skip, int feature_size);
+bool wide_features(int feature_size);
+
+// Joins the threads it holds when it goes out of scope (an exception from emplace_back or from a
+// later call leaves no joinable std::thread behind, which would call std::terminate).
+struct Joiner {
+  std::vector<std::thread> th;
+  ~Joiner() {
+    for (auto& t : th)
+      if (t.joinable()) t.join();
+  }
+};
+
+}  // namespace eegfx
+
+// the C ABI's opaque type lives in the global namespace; both sources that see its definition
+// use namespace eegfx throughout
+using namespace eegfx;
+
+struct eegfx_ctx {
+  int device = 0;
+  hipStream_t own = nullptr;
+  hipStream_t stream = nullptr;
+  int numerics = EEGFX_EXACT;
+  // Error word of the device-side position checks (fused.hip position_ok): host-mapped pinned
+  // memory the kernels store 1 into; eegfx_ctx_synchronize reports and clears it.
+  int* err_host = nullptr;
+  int* err_dev = nullptr;
+  size_t err_cap = 0;  // pinned_pool capacity of err_host
+  // the fma window kernel's guard strategy (guard.h EEGFX_TRACK_X), set by baseline_kernel in the
+  // same host-mapped block, 8 bytes past the error word
+  unsigned int* track_host() const { return (unsigned int*)((char*)err_host + 8); }
+  unsigned int* track_dev() const { return (unsigned int*)((char*)err_dev + 8); }
+  bool guard_track() const {
+    return EEGFX_TRACK_X == 2 ||
+           (EEGFX_TRACK_X == 1 && __atomic_load_n(track_host(), __ATOMIC_RELAXED) != 0);
+  }
+  bool timing = false;
+  // HIP event pairs bracketing each timed (dominant) kernel launch on the context stream, plus
+  // the algorithmic bytes each launch moved; summed by eegfx_ctx_kernel_stats.
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  std::vector<int64_t> event_bytes;
+  size_t n_timed = 0;
+  DevBuf raw, pos, out, scratch, fused;
+  DevBuf lr_x, lr_y, lr_state, lr_part, lr_mask;  // logistic regression (eegfx_logreg_*)
+  PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
+  PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
+                                         // a sharded provider's worker: the file spans it reads
+  // The fma numerics' conditioning guard (guard.h): device memory holding the flagged-row count
+  // of the current window_wide_kernel launch (first 128 B), then the running totals of recomputed
+  // rows and of rows that went to the second stage, each spread over kGuardSlots lines; the
+  // flagged-row list; guard_checked counts the rows that went through a guarded launch.
+  static constexpr size_t kGuardDevBytes = 128 + 2 * kGuardSlotBytes + 128;  // + Guard::adapt
+  int* guard_dev = nullptr;
+  DevBuf guard_list;
+  int64_t guard_checked = 0;
+  unsigned long long* guard_recomputed_slots() const {
+    return (unsigned long long*)((char*)guard_dev + 128);
+  }
+  unsigned long long* guard_rechecked_slots() const {
+    return (unsigned long long*)((char*)guard_dev + 128 + kGuardSlotBytes);
+  }
+  unsigned long long* guard_adapt() const {
+    return (unsigned long long*)((char*)guard_dev + 128 + 2 * kGuardSlotBytes);
+  }
+  Guard guard_for(int64_t n) {
+    if (numerics == EEGFX_EXACT) return Guard{nullptr, nullptr, nullptr};
+    guard_checked += n;
+    return Guard{guard_dev, (int64_t*)guard_list.get(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1)),
+                 guard_recomputed_slots(), guard_rechecked_slots(), guard_adapt(), track_dev()};
+  }
+  void bind_buffers() {
+    for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
+                      &lr_mask, &guard_list})
+      b->sp = &stream;
+  }
+  void release_buffers() {
+    for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
+                      &lr_mask, &guard_list})
+      b->release();
+    pin_in.release();
+    pin_out.release();
+    pin_chunk[0].release();
+    pin_chunk[1].release();
+  }
+  // streamed path (eegfx_process_recording_streamed): upload / download streams and the chunk
+  // events, created on first use and kept for the context's lifetime
+  hipStream_t up = nullptr, down = nullptr;
+  std::vector<hipEvent_t> copied, done;  // per device chunk buffer: uploaded / kernels done
+  // a provider's worker: the last upload out of each pin_chunk buffer, created on first use too
+  hipEvent_t staged[2] = {nullptr, nullptr};
+  void stream_resources(size_t ring) {
+    if (!up) {
+      HIP_CHECK(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+      HIP_CHECK(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
+    }
+    while (copied.size() < ring) {
+      hipEvent_t a = nullptr, b = nullptr;
+      HIP_CHECK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+      if (hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess) {
+        (void)hipEventDestroy(a);
+        fail(EEGFX_EHIP, "hipEventCreateWithFlags");
+      }
+      copied.push_back(a);
+      done.push_back(b);
+    }
+  }
+  // Completion of a small (latency-bound) call: spinning on an event query returns ~0.5 us sooner
+  // than hipStreamSynchronize (the drop-in bench's launch floor: 11.6 vs 12.2 us).  Past kSmallSpin
+  // the thread sleeps until the event completes (a blocking-sync event: interrupt-driven), so a
+  // waiter is not runnable: with more calling threads than cores (Spark local[*] on a CPU quota),
+  // runnable waiters kept threads whose work had completed off the cores for scheduler slices
+  // (profiles/r06/dropin_gate_ab.log).
+  static constexpr auto kSmallSpin = std::chrono::microseconds(EEGFX_SMALL_SPIN_US);
+  hipEvent_t small_done = nullptr;
+  void record_small() {
+    if (!small_done)
+      HIP_CHECK(hipEventCreateWithFlags(&small_done, hipEventDisableTiming | hipEventBlockingSync));
+    HIP_CHECK(hipEventRecord(small_done, stream));
+  }
+  void wait_small(bool recorded = false) {
+    if (!recorded) record_small();
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t e;
+    while ((e = hipEventQuery(small_done)) == hipErrorNotReady) {
+      if (std::chrono::steady_clock::now() - t0 > kSmallSpin) {
+#if EEGFX_SMALL_SLEEP_POLL
+        while ((e = hipEventQuery(small_done)) == hipErrorNotReady)
+          std::this_thread::sleep_for(std::chrono::microseconds(10));
+        break;
+#else
+        HIP_CHECK(hipEventSynchronize(small_done));
+        return;
+#endif
+      }
+    }
+    HIP_CHECK(e);
+  }
+  // The opt-in resident small-batch server (eegfx_ctx_set_mailbox, features_mailbox_kernel): a
+  // host-mapped command block, the kernel's own stream (never the context stream: the kernel
+  // stays resident), the request sequence and the time of the last request.  A server needs a
+  // hardware queue of its own (a queue runs its packets in order: a second kernel behind a
+  // resident one waits for it to idle out), and the highest-priority pool has kMbSlotsPerDevice of
+  // them, so at most that many contexts of the process hold a server slot on a device
+  // (mb_acquire); the others serve their calls on the launch path, and take a slot when one frees.
+  bool mailbox = false;   // enabled by the caller
+  bool mb_slot = false;   // holds one of the device's server slots
+  hipStream_t mb_stream = nullptr;
+  MailboxCmd* mb_host = nullptr;
+  MailboxCmd* mb_dev = nullptr;
+  size_t mb_cap = 0;  // pinned_pool capacity of mb_host
+  uint32_t mb_seq = 0;
+  uint32_t mb_gen = 0;      // launch generation (MailboxCmd::alive)
+  bool mb_live = false;     // launched and not stopped by the host (it may still have idled out)
+  bool mb_started = false;  // the live server has published its generation
+  bool mb_stuck = false;    // a server that did not start in time: stopped, not yet returned
+  std::chrono::steady_clock::time_point mb_last{};
+  static constexpr uint64_t kMbIdleTicks = 100000000;  // 1 s of s_memrealtime (100 MHz)
+  void mb_launch() {
+    // the staging a server reads is fixed for its lifetime (growing it stops the server first)
+    mb_host->rows = pin_in.p ? (const double*)pin_in.device_ptr() : nullptr;
+    mb_host->out = pin_out.p ? (double*)pin_out.device_ptr() : nullptr;
+    if (++mb_gen == 0) mb_gen = 1;
+    HIP_CHECK(launch_features_mailbox(mb_stream, mb_dev, kMbIdleTicks, mb_gen));
+    mb_live = true;
+    mb_started = false;
+  }
+  // Stops a live server: `stop` is seen within one poll.  A server that has not returned after
+  // 10 s (100 ms if it has not been seen to start: its queue is held by another resident kernel)
+  // keeps `stop` set, so it returns as soon as it runs, and is marked stuck; mb_ready clears
+  // `stop` once it has returned.
+  // Returns whether the kernel has returned.
+  bool mb_stop() {
+    if (!mb_host || !mb_live) return true;
+    __atomic_store_n(&mb_host->stop, 1u, __ATOMIC_RELEASE);
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t q;
+    while ((q = hipStreamQuery(mb_stream)) == hipErrorNotReady) {
+      if (std::chrono::steady_clock::now() - t0 >
+          (mb_started ? std::chrono::milliseconds(10000) : std::chrono::milliseconds(100))) {
+        mb_live = false;
+        mb_stuck = true;
+        return false;
+      }
+      std::this_thread::yield();
+    }
+    __atomic_store_n(&mb_host->stop, 0u, __ATOMIC_RELEASE);
+    mb_live = false;
+    HIP_CHECK(q);
+    return true;
+  }
+  // hipSuccess: the server kernel has returned; hipErrorNotReady: it is running; anything else
+  // is an error of the stream and is raised
+  bool mb_returned() {
+    const hipError_t q = hipStreamQuery(mb_stream);
+    if (q == hipErrorNotReady) return false;
+    HIP_CHECK(q);
+    return true;
+  }
+  // Whether the resident server takes this call (false: the launch path).  Takes a device slot
+  // and sets the server up on first use; restarts a server that may be near its 1 s idle exit
+  // (no request for 500 ms) so a request never races that exit; posts nothing until the server
+  // has published its generation, and falls back to the launch path (marking the server stuck)
+  // if it has not started within kMbStartWait.
+  static constexpr auto kMbStartWait = std::chrono::milliseconds(20);
+  bool mb_ready();
+  // One request: n epochs of packed window rows in pin_in -> rows in pin_out (after mb_ready).
+  void mb_serve(int64_t n, int C, int nfeat) {
+    MailboxCmd* m = mb_host;
+    if (++mb_seq == 0) mb_seq = 1;  // 0 means "no request" to the kernel
+    const auto now = std::chrono::steady_clock::now();
+    __atomic_store_n(&m->req, mailbox_request(mb_seq, C, nfeat, n), __ATOMIC_RELEASE);
+    for (uint64_t spin = 1;; ++spin) {
+      if (__atomic_load_n(&m->done, __ATOMIC_ACQUIRE) == mb_seq) break;
+      // as wait_small: a waiter past kSmallSpin sleeps between polls instead of staying runnable
+      if ((spin & 63) == 0 && std::chrono::steady_clock::now() - now > kSmallSpin)
+        std::this_thread::sleep_for(std::chrono::microseconds(10));
+      if ((spin & 4095) == 0) {
+        // a server that returned with the request pending (an error, or a stop from another
+        // path): serve it again on the same stream, after that kernel
+        if (mb_returned() && __atomic_load_n(&m->done, __ATOMIC_ACQUIRE) != mb_seq) mb_launch();
+        if (std::chrono::steady_clock::now() - now > std::chrono::seconds(30))
+          fail(EEGFX_EHIP, "mailbox request %u not served within 30 s", mb_seq);
+      }
+      __builtin_ia32_pause();
+    }
+    mb_last = std::chrono::steady_clock::now();
+  }
+  void release_mailbox();
+  void release_stream_resources() {
+    release_mailbox();
+    if (small_done) (void)hipEventDestroy(small_done);
+    small_done = nullptr;
+    for (hipEvent_t e : copied) (void)hipEventDestroy(e);
+    for (hipEvent_t e : done) (void)hipEventDestroy(e);
+    copied.clear();
+    done.clear();
+    for (hipEvent_t& e : staged) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    if (up) (void)hipStreamDestroy(up);
+    if (down) (void)hipStreamDestroy(down);
+    up = down = nullptr;
+  }
+
+  void activate() const { HIP_CHECK(hipSetDevice(device)); }
+  // Waits for the stream, then reports (and clears) a device-resident marker position that a
+  // kernel enqueued on this context since the last check refused: every API call that
+  // synchronises does this, so an invalid position surfaces at the first synchronising call
+  // after it (at the latest eegfx_ctx_synchronize), never silently.
+  void check_positions_flag() {
+    if (__atomic_exchange_n(err_host, 0, __ATOMIC_ACQ_REL) != 0)
+      fail(EEGFX_ERANGE,
+           "a device-resident marker position lies outside [100, n_frames + 100] "
+           "(OffLineDataProvider.java:220-225: ArrayIndexOutOfBoundsException); the rows of such "
+           "epochs are unspecified");
+  }
+  void drain() {
+    HIP_CHECK(hipStreamSynchronize(stream));
+    check_positions_flag();
+  }
+  void tic() {
+    if (!timing) return;
+    if (n_timed == events.size()) {
+      // timing only (read after the stream drains): no system-scope fence at each record, so
+      // the bracketed kernel's neighbours pay no cache writeback / invalidate for the timing
+      hipEvent_t a, b;
+      HIP_CHECK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+      HIP_CHECK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
+      events.emplace_back(a, b);
+      event_bytes.push_back(0);
+    }
+    HIP_CHECK(hipEventRecord(events[n_timed].first, stream));
+  }
+  void toc(int64_t bytes) {
+    if (!timing) return;
+    HIP_CHECK(hipEventRecord(events[n_timed].second, stream));
+    event_bytes[n_timed] = bytes;
+    ++n_timed;
+  }
+  void destroy_events() {
+    for (auto& e : events) {
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+    events.clear();
+    event_bytes.clear();
+    n_timed = 0;
+  }
+};
+
+namespace eegfx {
+
+// raw -> epochs + features (device pointers): the one-pass kernels when the layout fits them,
+// else the cut pass followed by the batch extract over the rows it wrote.  E: double or float epochs
+// (eegfx_process_recording_epochs / _f32): the same kernels, the same rows in `feat`.
+template <typename E>
+void run_epochs_and_features(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n_frames, int ct,
+                             const ChanSel& sel, int C, const int64_t* pos, int64_t n, E* ep,
+                             double* feat);
+
+}  // namespace eegfx

@@ -442,7 +442,17 @@ int eegfx_synth_recording(eegfx_ctx* ctx, int16_t* dst, int64_t n_frames, int32_
  * client of the reference is out of scope).  load_data never fails: like the reference
  * (:88-98) it stops at the first fatal error and keeps what was loaded; the message is
  * available from eegfx_odp_error(). */
-/* ctx may be NULL: a planning-only provider parses, selects and labels (positions, labels,
+/* The provider with one shard, on `ctx`: eegfx_odp_create_multi's provider over that one context
+ * (same planning pass, same worker, run on the calling thread), with the reference's sequential
+ * semantics in two places.  A repeated load_data appends: files, the Fz/Cz/Pz indices, the
+ * balance, the counters and the epochs of earlier loads persist as the reference's fields do
+ * (:53-60); the shard is reallocated once per load at its exact size and the rows it held are
+ * copied on the context stream (its `features` are dropped, and recomputed by get_features,
+ * once two loads ran under different numerics).  And the payload of every listed recording is
+ * opened where the reference reads it, in file order and ahead of the file's markers, so one
+ * that cannot be opened stops the load there (EEGFX_EIO) even if no epoch is selected from it;
+ * eegfx_odp_create_multi's workers open only the files their epochs come from.
+ * ctx may be NULL: a planning-only provider parses, selects and labels (positions, labels,
  * file indices) without reading the sample payload or touching a GPU. */
 int eegfx_odp_create(eegfx_ctx* ctx, const char* const* args, int32_t n_args, eegfx_odp** out);
 int eegfx_odp_load_data(eegfx_odp* odp);
@@ -474,16 +484,18 @@ void eegfx_odp_destroy(eegfx_odp* odp);
  * list.  Context r then owns the epochs eegfx_shard_range(n, r, n_ctx) of that list -- the
  * partition eegfx_gather_root expects of rank r, so a shard's `features` is a valid `local`
  * argument for it.  One worker thread per context that has epochs walks the files its range
- * intersects, reads only the frames eegfx_shard_span names for its positions in each file,
+ * intersects (a single such context: the calling thread), reads only the frames eegfx_shard_span
+ * names for its positions in each file,
  * uploads them and runs the one-pass kernels on its context's stream, into resident buffers
  * allocated once at their exact size.  Every context has been drained when load_data returns.
  *
  * All contexts must hold the same numerics at load_data (else EEGFX_EINVAL, nothing is loaded).
- * The call starts over: what an earlier load_data of the provider left is released first.
+ * The call starts over: what an earlier load_data of the provider left is released first
+ * (eegfx_odp_create's provider appends instead).
  * After the call num_epochs, positions, labels, file indices, the return code and the
  * eegfx_odp_error text equal those of eegfx_odp_create's provider on the same arguments (bit for
  * bit under EEGFX_EXACT; within the fma contract under EEGFX_FMA, whose guard strategy is
- * per-context state).  A failure a worker meets in file j (a payload read, a HIP error)
+ * per-context state), but for a payload that cannot be opened in a file no epoch comes from.  A failure a worker meets in file j (a payload read, a HIP error)
  * overrides an error planning found in file j or later and keeps only the epochs of the files
  * before j; the shard ranges are then the planned ranges clipped to what is kept -- the one
  * exception to the balanced partition.
@@ -500,7 +512,7 @@ int eegfx_odp_create_multi(eegfx_ctx* const* ctxs, int32_t n_ctx, const char* co
 
 /* The device view of one shard.  The pointers stay valid until the next eegfx_odp_load_data or
  * eegfx_odp_destroy of the provider and are complete when eegfx_odp_load_data returns.
- * eegfx_odp_create's provider has one shard: its own resident buffers. */
+ * eegfx_odp_create's provider has one shard, over everything it holds. */
 typedef struct {
   int32_t ctx_index;         /* index into ctxs                                                 */
   int32_t device;            /* HIP device of that context; -1 for a planning-only provider      */

@@ -9,10 +9,12 @@ import shutil
 import numpy as np
 
 from conftest import DATA
+from oracle import oracle
 
 CHANNELS7 = ("O1", "Cz", "F3", "Pz", "O2", "Fz", "C4")  # Fz, Cz, Pz outside the first 3 columns
 RES7 = (0.1, 0.25, 0.1, 0.5, 0.1, 0.125, 0.1)
 FZ_CZ_PZ = [CHANNELS7.index(n) for n in ("Fz", "Cz", "Pz")]
+SYN_ORDER = ["a_int16", "missing", "b_float", "c_vector", "d_rejected", "e_tail"]
 
 
 def two_file_info(tmp_path):
@@ -90,7 +92,26 @@ def synthetic_directory(tmp_path):
     ]
     for name, nf, fmt, vec, marks in specs:
         write_brainvision(d, name, synth(rng, nf, fmt), marks, fmt, vec)
-    order = ["a_int16", "missing", "b_float", "c_vector", "d_rejected", "e_tail"]
     info = tmp_path / "syn_info.txt"
-    info.write_text("".join(f"syn/{n}.eeg 1\n" for n in order))
+    info.write_text("".join(f"syn/{n}.eeg 1\n" for n in SYN_ORDER))
     return str(info)
+
+
+def oracle_plan(info, balance=0):
+    """What loadData selects from the files an info file lists, by the oracle alone: read_vmrk and
+    plan_markers per file in list order, the balance carried from file to file (and in from an
+    earlier load), a listed file that does not exist skipped.  The frames of a file come from its
+    size.  Returns (positions, labels, file indices, balance)."""
+    pos, lab, fid = [], [], []
+    for f, (name, guessed) in enumerate(oracle.load_info_txt(info).items()):
+        eeg = os.path.join(os.path.dirname(info), name)
+        if not os.path.isfile(eeg):
+            continue
+        h = oracle.read_vhdr(eeg[:-4] + ".vhdr")
+        frame = h["n_channels"] * (2 if h["binary_format"] == "INT_16" else 4)
+        p, l, balance = oracle.plan_markers(oracle.read_vmrk(eeg[:-4] + ".vmrk"),
+                                            os.path.getsize(eeg) // frame, guessed, balance)
+        pos += p
+        lab += l
+        fid += [f] * len(p)
+    return pos, lab, fid, balance

@@ -1,6 +1,10 @@
 """The OffLineDataProvider over several contexts (eegfx_odp_create_multi) against the one-context
 provider on the same arguments: bit for bit under EXACT numerics -- epochs, float32 epochs,
 labels, positions, file indices, features, return code and error text -- and against the oracle.
+Both providers run one implementation, so the comparisons alone would prove nothing: the
+one-context snapshot they compare with is itself checked against the oracle (the `synthetic`
+fixture), the error cases carry literal expectations, and the two behaviours that differ between
+the constructors (a repeated load, the payload check) are pinned on their own.
 
 Context i is created on device i % eegfx_device_count(): on a box that shows one GPU every
 context shares that device, so everything is exercised except the change of device between
@@ -12,7 +16,8 @@ import eeg_dataanalysispackage_amd as fx
 from eeg_dataanalysispackage_amd import _lib
 from eeg_dataanalysispackage_amd.sharding import native_shard_range
 from conftest import (DOD01, DOD02, EPOCH_SUM_GOLDEN, FEATURE_SUM_GOLDEN, INFO_TRAIN, hexrows)
-from odp_multi_data import synthetic_directory, two_file_info
+from odp_multi_data import (FZ_CZ_PZ, RES7, SYN_ORDER, oracle_plan, synthetic_directory,
+                            two_file_info)
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +104,24 @@ def oracle_rows_per_file(snap, bases):
     return np.concatenate(rows)
 
 
+def oracle_per_file(pos, fid, bases, cols, res):
+    """The oracle's epochs and rows for the positions each file contributes, in list order:
+    decode_epochs and process_recording on the file's own frames (a VECTORIZED file interleaved
+    by read_raw).  bases[f] is file f without its extension; a file without positions is not
+    opened (it may not exist)."""
+    epochs, rows = [np.zeros((0, 3, 750))], [np.zeros((0, 48))]
+    for f in sorted(set(fid)):
+        raw = fx.read_raw(bases[f] + ".vhdr", bases[f] + ".eeg")
+        own = [p for p, i in zip(pos, fid) if i == f]
+        epochs.append(oracle.decode_epochs(raw, cols, res, own))
+        rows.append(oracle.process_recording(raw, cols, res, own))
+    return np.concatenate(epochs), np.concatenate(rows)
+
+
+def syn_bases(info):
+    return [info[:-len("syn_info.txt")] + "syn/" + name for name in SYN_ORDER]
+
+
 def test_dod02_four_contexts(golden_vectors):
     args = [DOD02 + ".eeg", "4"]
     single, _, _ = load(args)
@@ -134,6 +157,12 @@ def synthetic(tmp_path_factory):
     nan_rows = np.flatnonzero(np.isnan(single["features"]).all(axis=1)).tolist()
     assert nan_rows == [5, 34] and single["pos"][5] == 3100 and single["pos"][34] == 6100
     assert np.all(single["epochs"][4][:, 300:] == single["epochs"][4][:, 300:301])  # padded tail
+    # the anchor of every comparison with `single` below: the oracle, not another provider
+    opos, olab, ofid, _ = oracle_plan(info)
+    assert single["pos"] == opos and single["labels"] == olab and single["fid"] == ofid
+    oep, orows = oracle_per_file(opos, ofid, syn_bases(info), FZ_CZ_PZ, [RES7[c] for c in FZ_CZ_PZ])
+    assert eq(single["epochs"], oep) and eq(single["features"], orows)
+    assert eq(single["epochs_f32"], oep.astype(np.float32))
     return info, single
 
 
@@ -183,6 +212,8 @@ def test_malformed_marker_in_the_second_of_three_files(tmp_path, field):
     single, _, rc1 = load([info])
     multi, shards, rc = load([info], 3)
     assert rc == rc1 == _lib.EEGFX_EFORMAT and multi["error"] == single["error"] != ""
+    assert single["error"] == ('For input string: "S 99999999999"' if field == "stimulus"
+                               else f"{vmrk}: bad marker position '15x0'")
     assert multi["n"] == (9 if field == "stimulus" else 6)
     assert_same(multi, single)
     assert_balanced(shards, multi["n"], 3)
@@ -213,11 +244,117 @@ def test_unreadable_payload_found_by_a_worker(tmp_path, later_planning_error):
     assert rc == rc1 and multi["error"] == single["error"]
     assert_same(multi, single)
     if unreadable:
-        assert rc == _lib.EEGFX_EIO and "cannot open" in multi["error"] and multi["n"] == 6
+        assert rc == _lib.EEGFX_EIO and single["error"] == "cannot open " + eeg and multi["n"] == 6
         planned = 15 if later_planning_error else 27     # 6 + 9 (+ 12 where e_tail parses)
         assert [(s[2], s[3]) for s in shards] == [
             (min(a, 6), min(b, 6) - min(a, 6))
             for a, b in (native_shard_range(planned, r, 3) for r in range(3))]
+
+
+def test_unopenable_payload_of_a_file_that_selects_no_epoch(tmp_path):
+    """d_rejected selects nothing.  The one-context provider reads every listed payload in file
+    order, so it stops there with EEGFX_EIO, keeps the 23 epochs before it and never loads
+    e_tail; the workers of a multi provider open only the files their epochs come from, so it
+    loads all 35."""
+    import os
+    info = synthetic_directory(tmp_path)
+    eeg = str(tmp_path / "syn" / "d_rejected.eeg")
+    os.chmod(eeg, 0)
+    try:
+        unreadable = not os.access(eeg, os.R_OK)
+        single, one, rc1 = load([info])
+        multi, shards, rc = load([info], 3)
+    finally:
+        os.chmod(eeg, 0o644)
+    opos, olab, ofid, _ = oracle_plan(info)
+    assert rc == _lib.EEGFX_OK and multi["error"] == "" and multi["n"] == 35
+    assert (multi["pos"], multi["labels"], multi["fid"]) == (opos, olab, ofid)
+    assert_balanced(shards, 35, 3)
+    if unreadable:
+        assert rc1 == _lib.EEGFX_EIO and single["error"] == "cannot open " + eeg
+        assert single["n"] == 23 and [s[3] for s in one] == [23]
+        assert (single["pos"], single["labels"], single["fid"]) == (opos[:23], olab[:23], ofid[:23])
+        assert eq(single["epochs"], multi["epochs"][:23])
+        assert eq(single["features"], multi["features"][:23])
+    else:
+        assert rc1 == _lib.EEGFX_OK
+        assert_same(multi, single)
+
+
+def test_one_context_provider_loaded_twice():
+    """A second loadData on eegfx_odp_create's provider appends (the reference's fields persist,
+    OffLineDataProvider.java:53-60): the first load's rows stay bit for bit, the balance carries
+    into the second, and the provider is still one shard over everything."""
+    ctx = fx.Context(0)
+    odp = fx.OffLineDataProvider([INFO_TRAIN], context=ctx)
+    odp.loadData()
+    first = snapshot(odp)
+    odp.loadData()
+    twice = snapshot(odp)
+    shards = [(v.ctx_index, v.device, v.first, v.count, v.features_numerics)
+              for v in odp.getShards()]
+    odp.close()
+    ctx.close()
+    plan = fx.OffLineDataProvider([INFO_TRAIN], plan_only=True)
+    plan.loadData()
+    plan.loadData()
+    ppos, pfid = plan.getPositions()
+    assert twice["error"] == "" and twice["n"] == plan.num_epochs() == 21 and first["n"] == 11
+    assert (twice["pos"], twice["fid"], twice["labels"]) == (ppos.tolist(), pfid.tolist(),
+                                                             plan.getDataLabels())
+    plan.close()
+    # two independent loads would repeat the first: the balance it left rejects a marker
+    assert twice["pos"] != first["pos"] * 2 and twice["pos"][:11] == first["pos"]
+    for key in ("epochs", "epochs_f32", "features"):
+        assert eq(twice[key][:11], first[key])
+    oep, orows = oracle_per_file(twice["pos"][11:], twice["fid"][11:], [DOD01], [0, 1, 2], [0.1] * 3)
+    assert eq(twice["epochs"][11:], oep) and eq(twice["features"][11:], orows)
+    assert shards == [(0, 0, 0, 21, _lib.EXACT)]
+
+
+def test_second_load_under_other_numerics_and_a_failing_second_load(tmp_path):
+    """Rows of two numerics are not served as one set: the shard view drops the features and
+    getFeatures recomputes them all.  A second load that fails in its second file keeps the
+    first load and the file before the failure."""
+    info = synthetic_directory(tmp_path)
+    (tmp_path / "syn_info.txt").write_text("syn/a_int16.eeg 1\nsyn/b_float.eeg 1\n")
+    ctx = fx.Context(0)
+    odp = fx.OffLineDataProvider([info], context=ctx)
+    odp.loadData()
+    first = snapshot(odp)
+    assert first["n"] == 15 and first["error"] == ""
+    p1, _, f1, balance = oracle_plan(info)
+    ctx.set_numerics("fma")
+    vmrk = tmp_path / "syn" / "b_float.vmrk"
+    vmrk.write_text(vmrk.read_text(encoding="utf-8") + "Mk99=Stimulus,S  1,15x0,1,0\n",
+                    encoding="utf-8")
+    assert fx.lib().eegfx_odp_load_data(odp._h) == _lib.EEGFX_EFORMAT
+    assert fx.lib().eegfx_odp_error(odp._h).decode() == f"{vmrk}: bad marker position '15x0'"
+    view = odp.getShards()[0]
+    assert (view.first, view.count, view.features_numerics) == (0, odp.num_epochs(), -1)
+    assert view.features.shape == (0, 48) and view.epochs.shape == (odp.num_epochs(), 3, 750)
+    pos, fid = odp.getPositions()
+    # file a again under the balance the first load left, nothing of file b
+    (tmp_path / "only_a.txt").write_text("syn/a_int16.eeg 1\n")
+    p2, l2, f2, _ = oracle_plan(str(tmp_path / "only_a.txt"), balance)
+    assert (p1, f1) == (first["pos"], first["fid"]) and len(p2) > 0
+    assert pos.tolist() == p1 + p2 and fid.tolist() == f1 + f2
+    assert odp.getDataLabels() == first["labels"] + l2
+    epochs = odp.getData()
+    assert eq(epochs[:15], first["epochs"])
+    bases = [str(tmp_path / "syn" / name) for name in ("a_int16", "b_float")]
+    res = [RES7[c] for c in FZ_CZ_PZ]
+    oep, orows = oracle_per_file(pos.tolist()[15:], fid.tolist()[15:], bases, FZ_CZ_PZ, res)
+    assert eq(epochs[15:], oep)
+    fma = odp.getFeatures()
+    ctx.set_numerics("exact")
+    exact = odp.getFeatures()
+    odp.close()
+    ctx.close()
+    nan = np.isnan(exact)
+    assert eq(exact[:15], first["features"]) and eq(exact[15:], orows)
+    assert np.array_equal(np.isnan(fma), nan)
+    assert np.max(np.abs(fma[~nan] - exact[~nan])) <= FMA_TOL
 
 
 def test_fma_rows_within_the_contract(synthetic):

@@ -1,6 +1,7 @@
 """The OffLineDataProvider over several contexts, host side only: the planning-only provider of
 eegfx_odp_create_multi (ctxs == NULL) reports the shard ranges a device run will use, with the
-same selection as the one-context planning provider; eegfx_shard_span; the argument checks.
+same selection as the one-context planning provider, which is checked against the oracle's plan;
+the one-context planning provider loaded twice; eegfx_shard_span; the argument checks.
 No GPU is touched."""
 import ctypes
 
@@ -11,7 +12,7 @@ import eeg_dataanalysispackage_amd as fx
 from eeg_dataanalysispackage_amd import _lib
 from eeg_dataanalysispackage_amd.sharding import native_shard_range, shard_span
 from conftest import DOD02, INFO_TRAIN
-from odp_multi_data import synthetic_directory, two_file_info
+from odp_multi_data import oracle_plan, synthetic_directory, two_file_info
 
 
 def plan(args, shards=None):
@@ -94,6 +95,38 @@ def test_synthetic_directory_plan(tmp_path):
     per_shard = [fid[v.first:v.first + v.count] for v in views]
     assert per_shard[1].count(0) == 1 and multi[1][5] == 3100   # pos - 100 == n_frames, alone
     assert sum(5 in files for files in per_shard) == 3
+
+
+def test_synthetic_directory_plan_against_the_oracle(tmp_path):
+    """The anchor of the comparisons between providers: the one-context plan is the oracle's."""
+    info = synthetic_directory(tmp_path)
+    (n, pos, fid, labels, error), _ = plan([info])
+    opos, olab, ofid, _ = oracle_plan(info)
+    assert error == "" and n == 35 == len(opos)
+    assert pos == opos and labels == olab and fid == ofid
+
+
+def test_one_context_planning_provider_loaded_twice():
+    """A second loadData on eegfx_odp_create's provider appends: files, channel indices, balance
+    and counters persist as the reference's fields do (OffLineDataProvider.java:53-60)."""
+    odp = fx.OffLineDataProvider([INFO_TRAIN], plan_only=True)
+    odp.loadData()
+    first = (odp.getPositions()[0].tolist(), odp.getDataLabels())
+    odp.loadData()
+    pos, fid = odp.getPositions()
+    pos, fid, labels = pos.tolist(), fid.tolist(), odp.getDataLabels()
+    views = odp.getShards()
+    assert odp.last_error == "" and odp.num_epochs() == len(pos) == 21
+    odp.close()
+    assert pos[:11] == first[0] and labels[:11] == first[1] and fid == [0] * 21
+    # the balance left by the first load (-1) rejects the leading non-target of the second:
+    # two independent loads would repeat the first
+    assert pos[11:] == first[0][1:] and labels[11:] == first[1][1:]
+    assert (pos, labels) != (first[0] * 2, first[1] * 2)
+    p1, l1, f1, balance = oracle_plan(INFO_TRAIN)
+    p2, l2, f2, _ = oracle_plan(INFO_TRAIN, balance)
+    assert balance == -1 and (pos, labels, fid) == (p1 + p2, l1 + l2, f1 + f2)
+    assert [(v.ctx_index, v.device, v.first, v.count) for v in views] == [(0, -1, 0, 21)]
 
 
 def span_formula(pos, n_frames):
@@ -179,5 +212,5 @@ def test_planning_error_keeps_the_prefix(tmp_path):
     vmrk.write_text("".join(lines), encoding="utf-8")
     single, _ = plan([info])
     multi, views = plan([info], shards=3)
-    assert multi == single and multi[4] != "" and 6 < multi[0] < 35
+    assert multi == single and multi[4] == 'For input string: "S 99999999999"' and multi[0] == 9
     check_plan_views(views, multi[0], 3)

@@ -8,7 +8,8 @@ Writes --files synthetic int16 recordings of --frames frames x 3 channels with a
 the median, minimum and maximum of --repeat loads per leg.  Recorded, with no threshold: on a box
 with one GPU the multi legs show only the overlap of file reads, uploads and kernels.
 
-    python tools/odp_multi_bench.py [--files 64] [--frames 1000000] [--json out.json]
+    python tools/odp_multi_bench.py [--lib path/to/libeegfx.so] [--files 64] [--frames 1000000]
+                                    [--json out.json]
 """
 import argparse
 import json
@@ -22,6 +23,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import eeg_dataanalysispackage_amd as fx  # noqa: E402
+from eeg_dataanalysispackage_amd import _lib  # noqa: E402
 
 
 def write_directory(root, files, frames, spacing):
@@ -69,6 +71,7 @@ def time_leg(make, repeat):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--lib", default=None, help="libeegfx.so to load (default: the package's)")
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--frames", type=int, default=1_000_000)
     ap.add_argument("--spacing", type=int, default=1000)
@@ -76,8 +79,10 @@ def main():
     ap.add_argument("--contexts", type=int, nargs="*", default=[1, 2, 4, 8])
     ap.add_argument("--json", default=None, help="also write the result to this file")
     a = ap.parse_args()
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     n_dev = fx.device_count()
-    result = {"devices": n_dev, "files": a.files, "frames": a.frames, "spacing": a.spacing,
+    result = {"lib": a.lib or "package", "devices": n_dev, "files": a.files, "frames": a.frames, "spacing": a.spacing,
               "repeat": a.repeat, "legs": {}}
     with tempfile.TemporaryDirectory() as root:
         info = write_directory(root, a.files, a.frames, a.spacing)
