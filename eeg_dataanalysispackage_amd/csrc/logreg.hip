@@ -55,6 +55,20 @@ __device__ __forceinline__ double grad_mult(double margin, double y) {
   }
 }
 
+// acc + mult * x, one row's term of the gradient.  HingeGradient runs its axpy only for a row
+// inside the hinge: any other row -- one whose margin is NaN included, since 1 > NaN is false --
+// has multiplier 0 and leaves the sum as it is, whatever the row holds (0 * NaN would be NaN).
+// LogisticGradient multiplies every row; its multiplier is never an exact 0 for a non-finite
+// margin, and it keeps the plain fma.
+template <int GRAD>
+__device__ __forceinline__ double axpy_row(double mult, double x, double acc) {
+  if constexpr (GRAD == 0) {
+    return __builtin_fma(mult, x, acc);
+  } else {
+    return mult != 0.0 ? __builtin_fma(mult, x, acc) : acc;
+  }
+}
+
 // Row r of iteration's sample (mask == nullptr: every row).
 __device__ __forceinline__ bool sampled(const uint32_t* __restrict__ mask, int64_t r) {
   return !mask || ((mask[r >> 5] >> (r & 31)) & 1u);
@@ -91,7 +105,7 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad_kernel(
     dot = wave_sum(dot);
     const double mult = grad_mult<GRAD>(dot, y[r]);
 #pragma unroll
-    for (int k = 0; k < KD; ++k) acc[k] = __builtin_fma(mult, x[k], acc[k]);
+    for (int k = 0; k < KD; ++k) acc[k] = axpy_row<GRAD>(mult, x[k], acc[k]);
   }
 #pragma unroll
   for (int k = 0; k < KD; ++k) acc_s[w][lane + 64 * k] = acc[k];
@@ -148,11 +162,14 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
     for (int u = 0; u < U; ++u) {
       // unconditional loads from clamped addresses (no exec-mask branch around a load, so all
       // U x FPL loads of the group issue before the first wait).  A row past n re-reads row
-      // n-1 and gets multiplier 0 below; a feature slot past d meets weight 0 and is never
-      // stored -- real data of the same rows, so non-finite inputs propagate as they would.
+      // n-1 and gets multiplier 0; a feature slot past d re-reads feature d-1, meets weight 0
+      // and is never stored.  With finite data both add exact zeros.  A re-read NaN or Inf
+      // would not (0 * NaN = NaN): it makes the margin of its row non-finite, and a wave that
+      // sees such a margin redoes its group the careful way below.
       // (Measured per gradient: hinge 0.114 -> 0.082 ms per iteration on 1M x 48; logistic,
       // whose exp the compiler already schedules the guarded loads around, keeps the guarded
-      // form: 0.087 vs 0.090 ms.)
+      // form: 0.087 vs 0.090 ms.  Taking the U margins before the first fma of the group, as
+      // the test below needs: hinge 0.085 -> 0.081 ms, profiles/logreg_shapes/.)
       const int64_t r = r0 + 4 * u + q;
       dot[u] = 0.0;
       if constexpr (GRAD == 0) {
@@ -176,13 +193,43 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
         yy[u] = y[r < n ? r : n - 1];
       }
     }
+    double mult[U], msum = 0.0;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const double m = row16_sum(dot[u]);
       const bool ok = r0 + 4 * u + q < n && sampled(mask, r0 + 4 * u + q);
-      const double mult = ok ? grad_mult<GRAD>(m, yy[u]) : 0.0;
+      mult[u] = ok ? grad_mult<GRAD>(m, yy[u]) : 0.0;
+      msum += m;  // non-finite as soon as one margin is
+    }
+    if constexpr (GRAD == 1) {
+      // A finite margin means every value loaded for the row is finite -- the re-read ones
+      // too, which met weight 0 -- and then fma(0, x, acc) == acc: the plain sums below are
+      // MLlib's.  A wave holding a non-finite margin (wave-uniform, so row16_sum's DPP still
+      // has all lanes) zeroes the slots past d, takes the margins again -- an Inf re-read for
+      // a slot past d made Inf * 0 = NaN of a margin that may be +-Inf -- and skips the rows
+      // with multiplier 0 as HingeGradient skips its axpy.
+      if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(msum) <= __DBL_MAX__)) != 0) {
 #pragma unroll
-      for (int k = 0; k < FPL; ++k) acc[k] = __builtin_fma(mult, x[u][k], acc[k]);
+        for (int u = 0; u < U; ++u) {
+          double dt = 0.0;
+#pragma unroll
+          for (int k = 0; k < FPL; ++k) {
+            if (j + 16 * k >= d) x[u][k] = 0.0;
+            dt = __builtin_fma(x[u][k], wv[k], dt);
+          }
+          const double m = row16_sum(dt);
+          const bool ok = r0 + 4 * u + q < n && sampled(mask, r0 + 4 * u + q);
+          const double mu = ok ? grad_mult<GRAD>(m, yy[u]) : 0.0;
+#pragma unroll
+          for (int k = 0; k < FPL; ++k) acc[k] = axpy_row<GRAD>(mu, x[u][k], acc[k]);
+        }
+        continue;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int k = 0; k < FPL; ++k) acc[k] = __builtin_fma(mult[u], x[u][k], acc[k]);
     }
   }
 #pragma unroll

@@ -19,7 +19,8 @@ The algorithm lives in an un-vendored dependency, ``org.apache.spark:spark-mllib
 * ``LogisticRegressionModel.predict``: 1.0 if 1 / (1 + exp(-(w.x + b))) > threshold (0.5).
 * ``SVMClassifier.train`` (Classification/SVMClassifier.java:83-111): ``SVMWithSGD`` -- the same
   GradientDescent / SquaredL2Updater loop and defaults with ``HingeGradient``: s = 2 label - 1;
-  a row with 1 > s * w.x adds -s x to the gradient, any other row adds nothing (the config_*
+  a row with 1 > s * w.x adds -s x to the gradient, any other row adds nothing -- a row whose
+  margin is NaN included: the comparison is false and the row is never multiplied (the config_*
   path passes config_reg_param through).  ``SVMModel.predict`` (:71): 1.0 if w.x + b > threshold
   (0.0), the margin itself without a threshold.
 * ``test`` (:117-141): MulticlassMetrics' 2x2 confusion matrix (rows = actual label, columns =
@@ -217,12 +218,19 @@ def sgd_train(X, y, num_iterations=DEFAULT_ITERS, step_size=DEFAULT_STEP, reg_pa
                 continue
             Xs, ys = X[rows], y[rows]
         if gradient == "hinge":
+            # HingeGradient's axpy runs only inside `if (1.0 > labelScaled * dotProduct)`: a row
+            # whose margin is NaN (a NaN feature, an Inf feature meeting a zero weight) fails the
+            # comparison and is skipped, so it is never multiplied.  The skipped rows stay as +0.0
+            # rows of the summed array, which keeps the summation order (and so, on finite
+            # inputs, every bit of the result) that of summing mult * x over all rows.
             s_lab = 2.0 * ys - 1.0
-            mult = np.where(1.0 > s_lab * (Xs @ w), -s_lab, 0.0)
+            sel = 1.0 > s_lab * (Xs @ w)
+            terms = np.zeros_like(Xs)
+            terms[sel] = -s_lab[sel, None] * Xs[sel]
         else:
             margin = -(Xs @ w)
-            mult = 1.0 / (1.0 + np.exp(margin)) - ys
-        grad = (mult[:, None] * Xs).sum(axis=0) / len(ys)
+            terms = (1.0 / (1.0 + np.exp(margin)) - ys)[:, None] * Xs
+        grad = terms.sum(axis=0) / len(ys)
         step = step_size / math.sqrt(i)
         w = w * (1.0 - step * reg_param)
         w = w - step * grad

@@ -1,4 +1,7 @@
-"""Non-finite, subnormal and extreme-magnitude inputs through every entry point and kernel family.
+"""Non-finite, subnormal and extreme-magnitude inputs through every epoch-to-feature entry point
+and kernel family.  (The classifier entry points -- eegfx_logreg_* / eegfx_svm_* on NaN and +-Inf
+feature rows and labels -- are in test_gpu_logreg_shapes.py, their oracle pinned by
+test_logreg_reference.py.)
 
 The judge is the CPU oracle, pinned on these very inputs by test_oracle_extremes.py.  One rule
 (check) everywhere:
