@@ -29,14 +29,6 @@ using namespace eegfx;
 
 #include "ctx.h"
 
-// A/B only: the small-call admission gate around the launch alone (the wait outside it)
-#ifndef EEGFX_GATE_LAUNCH_ONLY
-#define EEGFX_GATE_LAUNCH_ONLY 0
-#endif
-// A/B only: configs[4]'s marker positions uploaded beside the first chunk instead of before it
-#ifndef EEGFX_STREAM_POS_AFTER
-#define EEGFX_STREAM_POS_AFTER 0
-#endif
 
 namespace eegfx {
 
@@ -685,24 +677,12 @@ int extract_features_api(eegfx_ctx* ctx, const E* epochs, int64_t n, int32_t C, 
           memcpy(out, hout, out_bytes);
           return;
         }
-#if EEGFX_GATE_LAUNCH_ONLY
-        {
-          SmallCallGate gate(ctx->device);
-          ctx->tic();
-          HIP_CHECK(launch_features_small(ctx->stream, (const double*)ctx->pin_in.device_ptr(), n,
-                                          C, feature_size, (double*)ctx->pin_out.device_ptr()));
-          ctx->toc(0);
-          ctx->record_small();
-        }
-        ctx->wait_small(true);
-#else
         SmallCallGate gate(ctx->device);
         ctx->tic();
         HIP_CHECK(launch_features_small(ctx->stream, (const double*)ctx->pin_in.device_ptr(), n, C,
                                         feature_size, (double*)ctx->pin_out.device_ptr()));
         ctx->toc(0);
         ctx->wait_small();
-#endif
         ctx->check_positions_flag();
         memcpy(out, hout, out_bytes);
         return;
@@ -967,11 +947,8 @@ int eegfx_process_recording_streamed(eegfx_ctx* ctx, const void* raw, int32_t fm
     // copy on the context stream behind the first chunk's frames (7.44-7.48 against 7.13-7.16);
     // each pinned chunk as two halves on two upload streams (7.75-7.81 against 7.14).
     int64_t* d_pos = (int64_t*)ctx->pos.get(sizeof(int64_t) * (size_t)n);
-    auto upload_positions = [&] {
-      HIP_CHECK(hipMemcpyAsync(d_pos, spos, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice,
-                               ctx->stream));
-    };
-    if (!EEGFX_STREAM_POS_AFTER) upload_positions();
+    HIP_CHECK(hipMemcpyAsync(d_pos, spos, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice,
+                             ctx->stream));
     double* d_out = (double*)ctx->out.get(sizeof(double) * (size_t)(n * F));
     (void)ctx->fused.get(fused_scratch_bytes(n, C));  // every chunk's baselines fit: no realloc
     // chunk buffers: 64 B front pad (the kernels round the first quad down by < 16 B) + data
@@ -1038,7 +1015,6 @@ int eegfx_process_recording_streamed(eegfx_ctx* ctx, const void* raw, int32_t fm
         }
         if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
         HIP_CHECK(hipEventRecord(copied[b], cs));
-        if (EEGFX_STREAM_POS_AFTER && k == 0) upload_positions();  // beside the first chunk's
         HIP_CHECK(hipStreamWaitEvent(ctx->stream, copied[b], 0));
         // frame f of the recording lives at raw_dev + f*FB for lo <= f < hi (pointer arithmetic
         // only: nothing below dst is ever read)

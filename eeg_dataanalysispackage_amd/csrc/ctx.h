@@ -28,11 +28,6 @@
 #ifndef EEGFX_SMALL_SPIN_US
 #define EEGFX_SMALL_SPIN_US 30
 #endif
-// A/B only: a small call's waiter past the spin polls its event between 10-us sleeps instead of
-// sleeping in the runtime's blocking-sync wait
-#ifndef EEGFX_SMALL_SLEEP_POLL
-#define EEGFX_SMALL_SLEEP_POLL 0
-#endif
 
 namespace eegfx {
 
@@ -248,25 +243,16 @@ struct eegfx_ctx {
   // (profiles/r06/dropin_gate_ab.log).
   static constexpr auto kSmallSpin = std::chrono::microseconds(EEGFX_SMALL_SPIN_US);
   hipEvent_t small_done = nullptr;
-  void record_small() {
+  void wait_small() {
     if (!small_done)
       HIP_CHECK(hipEventCreateWithFlags(&small_done, hipEventDisableTiming | hipEventBlockingSync));
     HIP_CHECK(hipEventRecord(small_done, stream));
-  }
-  void wait_small(bool recorded = false) {
-    if (!recorded) record_small();
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e;
     while ((e = hipEventQuery(small_done)) == hipErrorNotReady) {
       if (std::chrono::steady_clock::now() - t0 > kSmallSpin) {
-#if EEGFX_SMALL_SLEEP_POLL
-        while ((e = hipEventQuery(small_done)) == hipErrorNotReady)
-          std::this_thread::sleep_for(std::chrono::microseconds(10));
-        break;
-#else
         HIP_CHECK(hipEventSynchronize(small_done));
         return;
-#endif
       }
     }
     HIP_CHECK(e);

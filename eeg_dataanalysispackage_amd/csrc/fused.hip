@@ -26,16 +26,20 @@
 //                   per-epoch LDS layout whose strides keep every half-wave of ds_read_u16 on
 //                   distinct banks; each lane folds the window's sub-16-byte misalignment into
 //                   its read base.  Lanes decode (float)raw*res - b two samples at a time just in
-//                   time inside level 1 and run the cascade (fma numerics: partial-sum halos,
-//                   dwt8_fast_cascade; EXACT: value halos in the reference's order), and one wave
-//                   normalises the 8 x 48 features (EXACT: sequential sum of squares,
+//                   time and run the filter bank (fma numerics: levels 1-5 collapsed,
+//                   dwt8_collapsed_cascade; EXACT: value halos in the reference's order).  fma:
+//                   every channel wave normalises and stores its 16 features of each row from
+//                   registers, the conditioning guard (guard.h) testing each row; EXACT: one wave
+//                   normalises the 8 x 48 features (sequential sum of squares,
 //                   SignalProcessing.java:38-52) and stores them as contiguous wave stores.
 //
 // The alternatives measured against this pair (persistent, work-queue, two-sub-tile and
 // loader/consumer variants, the baselines folded into the window kernel, the collapsed operator
-// on the FP64 matrix cores, the register-direct window) are kept as patches under
-// tools/probes/history/ with their numbers in
-// DESIGN.md §6; none of them ships.
+// on the FP64 matrix cores, the register-direct window, the six-point form with 4 lanes per
+// signal, rows through LDS under fma) are kept as patches under tools/probes/history/ with their
+// numbers in tools/probes/HISTORY.md and DESIGN.md §6; none of them ships.  A rejected variant
+// goes there, not behind a compile-time switch: the switches left choose code only for the live
+// ablation study (EEGFX_GUARD, EEGFX_COLLAPSED, EEGFX_TOOM) and the guard strategy (EEGFX_TRACK_X).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -229,10 +233,6 @@ __device__ __forceinline__ void cascade_lds(const int16_t* own, const int16_t* n
     if constexpr (TRACK) {
       dwt8_collapsed_cascade<true>([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a6,
                                    d6, ymax);
-    } else if constexpr (EEGFX_LDS_B64 && CT == 3) {
-      typedef uint64_t u64_a2 __attribute__((aligned(2)));
-      dwt8_collapsed_cascade_b64([&](int k) { return *(const u64_a2*)(own + k * CT); }, r, b,
-                                 gbase, s, a6, d6);
     } else {
       dwt8_collapsed_cascade([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a6, d6);
     }
@@ -277,24 +277,24 @@ struct DmaRows {
 // DMAs) before the first DMA, so the DMAs leave back to back; an epoch whose window lies wholly
 // inside the recording (bit 0 of its word clear) takes the unguarded path.  Returns whether some
 // quad of this lane could not be DMA'd (the window reaches past either end of the recording).
-template <int CT, int C, bool NT, int SUB = kSub>
+template <int CT, int C, bool NT>
 __device__ __forceinline__ bool dma_issue(const uint8_t* __restrict__ raw, int64_t nbytes,
                                           const int64_t* __restrict__ wb, int64_t e0, int ne,
                                           uint32_t* win, int w, int lane, const DmaRows<CT>& rows) {
   using G = Geometry<CT>;
   constexpr int PER_E = DmaRows<CT>::PER_E;
-  constexpr int NE = (SUB + C - 1) / C;
+  constexpr int NE = (kSub + C - 1) / C;
   int64_t W[NE];
 #pragma unroll
   for (int t = 0; t < NE; ++t) {  // unconditional (clamped) loads: one scalar round trip
-    const int e = w + t * C < SUB ? w + t * C : SUB - 1;
+    const int e = w + t * C < kSub ? w + t * C : kSub - 1;
     W[t] = wb[e0 + (e < ne ? e : ne - 1)];
   }
   bool need_fix = false;
 #pragma unroll
   for (int t = 0; t < NE; ++t) {
     const int e = w + t * C;
-    if (e >= SUB || e >= ne) continue;  // uniform
+    if (e >= kSub || e >= ne) continue;  // uniform
     const int64_t Bq = W[t] & ~(int64_t)15;
     const uint8_t* sb = raw + Bq;
     uint32_t* dst = win + e * G::ESTR;
@@ -319,13 +319,13 @@ __device__ __forceinline__ bool dma_issue(const uint8_t* __restrict__ raw, int64
 
 // Direct (non-DMA) fill of the quads dma_issue skipped (same wave -> epoch mapping): zero or
 // partial quads at either end of the recording.
-template <int CT, int C, int SUB = kSub>
+template <int CT, int C>
 __device__ __forceinline__ void dma_fixup(const uint8_t* __restrict__ raw, int64_t nbytes,
                                           const int64_t* __restrict__ wb, int64_t e0, int ne,
                                           uint32_t* win, int w, int lane, const DmaRows<CT>& rows) {
   using G = Geometry<CT>;
   constexpr int PER_E = DmaRows<CT>::PER_E;
-  for (int e = w; e < SUB; e += C) {
+  for (int e = w; e < kSub; e += C) {
     if (e >= ne) break;
     const int64_t Bq = wb[e0 + e] & ~(int64_t)15;
 #pragma unroll
@@ -337,62 +337,32 @@ __device__ __forceinline__ void dma_fixup(const uint8_t* __restrict__ raw, int64
   }
 }
 
-// SUBS sub-tiles (8 epochs x C channels each) per workgroup of C * SUBS waves: wave w works on
-// channel w % C of sub-tile w / C.  The windows land by LDS-DMA (NT: non-temporal, when
-// neighbouring windows do not overlap); after the barrier that publishes them each lane decodes
-// its 64 + 8 samples straight from LDS inside level 1, the cascade runs in registers with
-// cross-lane halos (ds_bpermute), the a6/d6 rows overwrite the start of their sub-tile's window
-// buffer once every wave has read its samples (26 KB of LDS per sub-tile: 6 sub-tiles, 18 waves
-// per CU), and one wave per sub-tile normalises and stores its 8 rows.  Each sub-tile's LDS is
-// laid out as a one-sub-tile workgroup's; the sub-tiles of a workgroup share only its barriers
-// and its dispatch.
-#ifndef EEGFX_WIN_SUBS
-#define EEGFX_WIN_SUBS 1
-#endif
-// the guard's second stage in the 3-channel window kernel: every flagged row of a sub-tile in one
-// pass (recheck_c3_rows), or (0, A/B builds) one row at a time (recheck_c3)
-#ifndef EEGFX_RECHECK_ROWS
-#define EEGFX_RECHECK_ROWS 1
-#endif
-// fma numerics: each channel wave normalises and stores its own 16 features of every row from
-// registers (the row's sum of squares combined through LDS), and the guard's second stage runs on
-// all channel waves against the windows still staged (window_rows_fast); 0 (A/B builds): the rows
-// go through LDS and one wave normalises, guards and stores them (normalise_store)
-#ifndef EEGFX_REG_ROWS
-#define EEGFX_REG_ROWS 1
-#endif
-// Newton steps after v_rsq_f64 in the register-rows normalisation (1; 2 in A/B builds)
-#ifndef EEGFX_RSQ_STEPS
-#define EEGFX_RSQ_STEPS 1
-#endif
-// EEGFX_TRACK_X (guard.h): the guard's second-stage strategy of the fma window kernel.
-
 // The guard's second stage for channel `col` of the flagged rows of a sub-tile, by one channel
-// wave: the flagged rows (bit LPS e of `flagged` = epoch e, LPS lanes per signal)
-// share the wave, L = 64, 32, 16, 8 or 4 lanes per row for 1, 2, 3-4, 5-8 or 9-16 rows; each lane
+// wave: the flagged rows (bit 8 e of `flagged` = epoch e, 8 lanes per signal)
+// share the wave, L = 64, 32, 16 or 8 lanes per row for 1, 2, 3-4 or 5-8 rows; each lane
 // reads 512 / L consecutive frames of its row's window as staged in LDS (segment s at 16 SEGQ s
 // bytes past the epoch's misalignment) and keeps the column's min and max raw sample; those two
 // are decoded exactly as the kernel decodes every sample (x = fl(fl(raw * r) - b) is monotone in
 // raw), and X_c = max |x| is reduced over the row's lanes.  Returns X_c^2 on the lane sub == 0 of
 // each row's slot (0 elsewhere) and the epoch of the lane's slot in *row (-1 for lanes without
-// one).  delta, b: the misalignment and baseline of the lane's epoch (lane / LPS), shuffled to the
+// one).  delta, b: the misalignment and baseline of the lane's epoch (lane / 8), shuffled to the
 // slot's epoch.
-template <int FB, int SEGQ, int EBYTES, int SUB = kSub, int LPS = 8>
+template <int FB, int SEGQ, int EBYTES>
 __device__ __forceinline__ double channel_x2_rows(uint64_t flagged, const uint8_t* win, int col,
                                                   float r, float b, int delta, int lane,
                                                   int* row) {
-  static_assert(SUB * LPS == 64 && SUB <= 16, "one wave per channel, 4-bit epoch slots");
+  static_assert(kSub * 8 == 64, "one wave per channel, 8 lanes per signal");
   uint64_t T = 0;
   int k = 0;
 #pragma unroll
-  for (int e = 0; e < SUB; ++e)
-    if ((flagged >> (LPS * e)) & 1ull) { T |= (uint64_t)e << (4 * k); ++k; }
-  const int sh = k <= 1 ? 6 : k <= 2 ? 5 : k <= 4 ? 4 : k <= 8 ? 3 : 2;  // log2(L)
+  for (int e = 0; e < kSub; ++e)
+    if ((flagged >> (8 * e)) & 1ull) { T |= (uint64_t)e << (4 * k); ++k; }
+  const int sh = k <= 1 ? 6 : k <= 2 ? 5 : k <= 4 ? 4 : 3;  // log2(L)
   const int j = lane >> sh, sub = lane & ((1 << sh) - 1);
   const bool valid = j < k;
   const int e = valid ? (int)((T >> (4 * j)) & 15u) : (int)(T & 15u);
-  const int de = __shfl(delta, LPS * e, 64);
-  const float be = __shfl(b, LPS * e, 64);
+  const int de = __shfl(delta, 8 * e, 64);
+  const float be = __shfl(b, 8 * e, 64);
   const uint8_t* p0 = win + e * EBYTES + de + 2 * col;
   int mn = 32767, mx = -32768;
   // FPL = 512 / L frames per lane (a multiple of 8: runs never cross a segment), one fully unrolled
@@ -416,8 +386,7 @@ __device__ __forceinline__ double channel_x2_rows(uint64_t flagged, const uint8_
     case 6: scan(std::integral_constant<int, 8>()); break;
     case 5: scan(std::integral_constant<int, 16>()); break;
     case 4: scan(std::integral_constant<int, 32>()); break;
-    case 3: scan(std::integral_constant<int, 64>()); break;
-    default: scan(std::integral_constant<int, 128>()); break;
+    default: scan(std::integral_constant<int, 64>()); break;
   }
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   // (min, max) decoded as one pair: packed fp32 multiply and add, each lane rounded as the scalar
@@ -428,7 +397,7 @@ __device__ __forceinline__ double channel_x2_rows(uint64_t flagged, const uint8_
   uint32_t u = __float_as_uint(fmaxf(fabsf(x.x), fabsf(x.y)));
   u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0xB1, 0xF, 0xF, true));
   u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x4E, 0xF, 0xF, true));
-  if (sh >= 3) u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x141, 0xF, 0xF, true));
+  u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x141, 0xF, 0xF, true));
   if (sh >= 4) u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x140, 0xF, 0xF, true));
   if (sh >= 5) u = max(u, (uint32_t)__shfl_xor((int)u, 16, 64));
   if (sh >= 6) u = max(u, (uint32_t)__shfl_xor((int)u, 32, 64));
@@ -436,46 +405,51 @@ __device__ __forceinline__ double channel_x2_rows(uint64_t flagged, const uint8_
   *row = valid && sub == 0 ? e : -1;
   return X * X;
 }
-template <int CT, int C, bool FAST, bool NT, int SUBS = EEGFX_WIN_SUBS, bool TRK = false>
-__global__ __launch_bounds__(64 * C * SUBS, (5 + SUBS - 1) / SUBS) void window_kernel(
+
+// One sub-tile (8 epochs x C channels) per workgroup of C waves, wave w = channel w.  The windows
+// land by LDS-DMA (NT: non-temporal, when neighbouring windows do not overlap); after the barrier
+// that publishes them each lane decodes its 64 samples straight from LDS inside level 1 and the
+// cascade runs in registers with cross-lane halos (ds_bpermute).  26 KB of LDS: 6 workgroups,
+// 18 waves per CU.
+//   fma:   every channel wave normalises and stores its own 16 features of each row from
+//          registers (the row's sum of squares combined through LDS), and the guard's second
+//          stage runs on all channel waves against the windows still staged -- scanning them
+//          (channel_x2_rows) or, TRK, from the max |x| every lane tracked while decoding
+//          (EEGFX_TRACK_X, guard.h).
+//   EXACT: the a6/d6 rows overwrite the start of the window buffer once every wave has read its
+//          samples, and wave 0 normalises and stores the 8 rows (rows.h normalise_store).
+template <int CT, int C, bool FAST, bool NT, bool TRK = false>
+__global__ __launch_bounds__(64 * C, 5) void window_kernel(
     const uint8_t* __restrict__ raw, int64_t n_frames, ChanSel sel, const int64_t* __restrict__ wb,
     const float* __restrict__ base, int64_t n, double* __restrict__ out, Guard guard) {
   using G = Geometry<CT>;
   constexpr int F = C * 16;
   static_assert(kSub * F * 8 <= kSub * G::ESTR * 4, "feature rows alias the window buffer");
-  __shared__ __attribute__((aligned(16))) uint32_t win_all[SUBS * kSub * G::ESTR];
-  __shared__ double norm_all[SUBS * kSub];
-  __shared__ double gx_all[FAST ? SUBS * kSub * C : 1];  // the guard's X^2 per signal (fma)
-  // the REG guard paths synchronise the whole workgroup: one sub-tile only
-  constexpr bool REG = FAST && EEGFX_REG_ROWS && SUBS == 1;
-  __shared__ double part_all[REG ? SUBS * kSub * C : 1];  // per-signal sums of squares (REG)
-  __shared__ double xs_all[REG ? SUBS * kSub * C : 1];    // measured X_c^2 of flagged rows (REG)
+  __shared__ __attribute__((aligned(16))) uint32_t win[kSub * G::ESTR];
+  __shared__ double norm[kSub];                 // the rows' norms (EXACT)
+  __shared__ double gx[FAST ? kSub * C : 1];    // the guard's X^2 per signal (fma)
+  __shared__ double part[FAST ? kSub * C : 1];  // per-signal sums of squares (fma)
+  __shared__ double xs[FAST ? kSub * C : 1];    // measured X_c^2 of flagged rows (fma)
   const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = SUBS > 1 ? wid / C : 0, w = SUBS > 1 ? wid - h * C : wid;  // sub-tile, channel
-  uint32_t* win = win_all + h * kSub * G::ESTR;
-  double* norm = norm_all + h * kSub;
-  double* gx = gx_all + (FAST ? h * kSub * C : 0);
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // channel
   const int el = lane >> 3, s = lane & 7;
   const int64_t nbytes = n_frames * G::FB;
   const int col = sel.col[w];
   const float r = sel.res[w];
-  const int64_t e0 = ((int64_t)xcd_tile(blockIdx.x, gridDim.x) * SUBS + h) * kSub;
-  const int64_t rest = n - e0;  // >= 1 for the first sub-tile; a later one may be empty
-  const int ne = rest <= 0 ? 0 : (rest >> 31) != 0 ? kSub : ((int)rest < kSub ? (int)rest : kSub);
+  const int64_t e0 = (int64_t)xcd_tile(blockIdx.x, gridDim.x) * kSub;
+  const int64_t rest = n - e0;  // >= 1: the grid is ceil(n / kSub) tiles, xcd_tile a bijection
+  const int ne = (rest >> 31) != 0 ? kSub : ((int)rest < kSub ? (int)rest : kSub);
 
   const bool mine = el < ne;
   // This lane's baseline and window word: loaded unconditionally (clamped to a valid epoch) and
   // used only once the window DMAs are in flight, so the prologue waits on one round trip (the
   // window words' scalar loads) before the DMAs leave instead of three.
-  const int64_t ec = SUBS > 1 && ne == 0 ? n - 1 : e0 + (mine ? el : ne - 1);
+  const int64_t ec = e0 + (mine ? el : ne - 1);
   const float b_ld = base[ec * C + w];
   const uint32_t w_ld = (uint32_t)wb[ec];
   const DmaRows<CT> rows(lane);
-  if (SUBS == 1 || ne > 0) {  // wave-uniform
-    if (dma_issue<CT, C, NT>(raw, nbytes, wb, e0, ne, win, w, lane, rows))
-      dma_fixup<CT, C>(raw, nbytes, wb, e0, ne, win, w, lane, rows);
-  }
+  if (dma_issue<CT, C, NT>(raw, nbytes, wb, e0, ne, win, w, lane, rows))
+    dma_fixup<CT, C>(raw, nbytes, wb, e0, ne, win, w, lane, rows);
   const float b = mine ? b_ld : 0.0f;
   const int delta = mine ? (int)(w_ld & 14u) : 0;
   if (FAST && EEGFX_GUARD && (lane & 7) == 0) gx[el * C + w] = guard_x2_int16(r, b);  // read after the barriers
@@ -486,24 +460,20 @@ __global__ __launch_bounds__(64 * C * SUBS, (5 + SUBS - 1) / SUBS) void window_k
   double a6 = 0.0, d6 = 0.0;
   // TRK: this launch tracks max |x| (EEGFX_TRACK_X, guard.h) -- a variant of its own, so the
   // scanning launches carry no second filter loop
-  constexpr bool TRACKABLE = REG && TRK && EEGFX_GUARD;
+  constexpr bool TRACKABLE = FAST && TRK && EEGFX_GUARD;
   constexpr bool track = TRACKABLE;  // (no flag is raised without guard.total either way)
   float ymax = 0.0f;
-  if (SUBS == 1 || ne > 0) {
-    const uint8_t* eb = (const uint8_t*)(win + el * G::ESTR) + delta + 2 * col;
-    const int16_t* own = (const int16_t*)(eb + 16 * G::SEGQ * s);
-    const int16_t* nxt = (const int16_t*)(eb + 16 * G::SEGQ * ((s + 1) & 7));
-    cascade_lds<CT, FAST, TRACKABLE>(own, nxt, r, b, lane & ~7, s, a6, d6, &ymax);
-  }
+  const uint8_t* eb = (const uint8_t*)(win + el * G::ESTR) + delta + 2 * col;
+  const int16_t* own = (const int16_t*)(eb + 16 * G::SEGQ * s);
+  const int16_t* nxt = (const int16_t*)(eb + 16 * G::SEGQ * ((s + 1) & 7));
+  cascade_lds<CT, FAST, TRACKABLE>(own, nxt, r, b, lane & ~7, s, a6, d6, &ymax);
 
-  if constexpr (REG) {
+  if constexpr (FAST) {
     // Each channel wave keeps its 16 features of each row in registers: the row's sum of squares
     // is the three channels' shares, combined through LDS in channel order (the same value in
     // every wave), and every wave normalises and stores its own part -- 8 lines of 128 B, a6 then
     // d6 of its channel -- so the staged windows stay intact for the guard's second stage, which
     // then runs on all channel waves at once.
-    double* part = part_all + h * kSub * C;
-    double* xs = xs_all + h * kSub * C;
     const double q = group8_sum(__builtin_fma(a6, a6, d6 * d6));
     if constexpr (track) {
       // the signal's measured X_c = max |x| over its 8 lanes (|x| >= 0 orders like its bits)
@@ -560,7 +530,7 @@ __global__ __launch_bounds__(64 * C * SUBS, (5 + SUBS - 1) / SUBS) void window_k
         if (left) guard_count_recomputed(guard, (unsigned long long)__popcll(left));
       }
     }
-    const double inv = EEGFX_RSQ_STEPS == 1 ? rsqrt_nr1(acc) : rsqrt_nr(acc);
+    const double inv = rsqrt_nr1(acc);
     if (mine && !((left >> (8 * el)) & 1ull)) {
       double* o = out + (e0 + el) * F + w * 16 + s;
       __builtin_nontemporal_store(a6 * inv, o);
@@ -595,172 +565,20 @@ __global__ __launch_bounds__(64 * C * SUBS, (5 + SUBS - 1) / SUBS) void window_k
         __syncthreads();
       }
     }
-    return;
-  }
-  double* fb = (double*)win;
-  __syncthreads();  // every wave has read its samples: the rows may overwrite the window
-  // the row slot is recomputed here from an opaque copy of the lane id, so its address is not
-  // kept live across the filter bank (it was the one spilled VGPR)
-  int l2 = lane;
-  asm volatile("" : "+v"(l2));
-  const int slot = (l2 >> 3) * F + w * 16 + (l2 & 7);
-  fb[slot] = a6;
-  fb[slot + 8] = d6;
-  __syncthreads();
-  if (w == 0 && (SUBS == 1 || ne > 0)) {
-    // the guard's rare path: the row recomputed under EXACT from the recording by this wave, with
-    // the LDS past the 8 feature rows of its sub-tile as scratch (every other wave is done with
-    // this sub-tile's window)
-    auto redo = [&](int e, double* row) {
-      const int64_t B = wb[e0 + e] & ~(int64_t)1;  // byte offset of the window (frame pos + 175)
-      const int64_t f0 = B / G::FB;
-      dwt8_exact_row_wave(
-          [&](int c, int k) {
-            const float rc = sel.res[c], bc = base[(e0 + e) * C + c];
-            const float v = f0 + k < n_frames
-                                ? (float)*(const int16_t*)(raw + B + (int64_t)k * G::FB + 2 * sel.col[c])
-                                : 0.0f;
-            float y = v * rc;
-            y = y - bc;
-            return (double)y;
-          },
-          C, 16, fb + kSub * F, row, lane);
-    };
-    // the guard's second stage: the rows' measured max |x|, from the staged windows (epochs
-    // 1-7, recheck_c3_rows: every flagged row of the sub-tile in one pass; epoch 0's window lies
-    // under the rows: from the recording, recheck_c3)
-#if EEGFX_RECHECK_ROWS
-    auto recheck = [&](uint64_t flagged, double acc) {
-      return recheck_c3_rows<G::SEGQ, G::ESTR * 4>(
-          flagged, acc, sel, base + e0 * C, (const uint8_t*)win, delta, lane, [&] {
-            return recheck_c3<G::FB, G::SEGQ>(raw, n_frames, sel, wb[e0], base + e0 * C,
-                                              nullptr, true, lane);
-          });
-    };
-    normalise_store<F, FAST, C>(fb, norm, out + e0 * F, ne, lane, gx, guard, redo, recheck);
-#else
-    auto recheck = [&](int e) {
-      return recheck_c3<G::FB, G::SEGQ>(raw, n_frames, sel, wb[e0 + e], base + (e0 + e) * C,
-                            (const uint8_t*)(win + e * G::ESTR), e == 0, lane);
-    };
-    normalise_store<F, FAST, C>(fb, norm, out + e0 * F, ne, lane, gx, guard, redo,
-                                per_row_recheck(recheck));
-#endif
-  }
-}
-
-// fma numerics, 3-channel int16 recordings, A/B builds (-DEEGFX_WIN4=1): the six-point form with
-// 4 lanes per signal (dwt8.h dwt8_toom6_core).  A channel wave holds 16 epochs and a workgroup
-// (3 waves, wave w = channel w) a 16-epoch sub-tile: 51 KB of staged windows in window_kernel's
-// per-epoch layout, three workgroups per CU.  Each lane reads its 128 samples (two segments)
-// straight from LDS; the rows are normalised and stored from registers by every channel wave
-// (a6[2 s], a6[2 s + 1], d6[2 s], d6[2 s + 1] of its channel: two 16-byte stores per lane), and the
-// guard's second stage scans the staged windows on all channel waves.  8.9 % fewer VALU
-// instructions than window_kernel (SQ_INSTS_VALU) but 2.5 % slower per step: with half the waves
-// per CU the window DMA is no longer covered by other workgroups' work (the kernel without its DMA
-// runs in 0.56 ms); persistent forms that overlap the next sub-tile's DMA themselves measured
-// slower still (DESIGN_LOG.md §R6).
-#ifndef EEGFX_WIN4
-#define EEGFX_WIN4 0
-#endif
-constexpr int kSub4 = 16;  // epochs per sub-tile of window4_kernel (16 epochs x 4 lanes = 64 lanes)
-
-template <bool NT>
-__global__ __launch_bounds__(192, 3) void window4_kernel(
-    const uint8_t* __restrict__ raw, int64_t n_frames, ChanSel sel, const int64_t* __restrict__ wb,
-    const float* __restrict__ base, int64_t n, double* __restrict__ out, Guard guard) {
-  using G = Geometry<3>;
-  constexpr int C = 3, F = C * 16, SUB = kSub4, LPS = kLanesPerSignal4;
-  static_assert(SUB * LPS == 64, "one wave per channel");
-  __shared__ __attribute__((aligned(16))) uint32_t win[SUB * G::ESTR];
-  __shared__ double gx[SUB * C];    // the guard's a-priori X^2 per signal
-  __shared__ double part[SUB * C];  // per-signal sums of squares
-  __shared__ double xs[SUB * C];    // measured X_c^2 of flagged rows
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // channel
-  const int el = lane >> 2, s = lane & 3;
-  const int64_t nbytes = n_frames * G::FB;
-  const int col = sel.col[w];
-  const float r = sel.res[w];
-  const int64_t e0 = (int64_t)xcd_tile(blockIdx.x, gridDim.x) * SUB;
-  const int64_t rest = n - e0;  // >= 1
-  const int ne = rest >= SUB ? SUB : (int)rest;
-  const bool mine = el < ne;
-  const int64_t ec = e0 + (mine ? el : ne - 1);
-  const float b_ld = base[ec * C + w];
-  const uint32_t w_ld = (uint32_t)wb[ec];
-  const DmaRows<3> rows(lane);
-  if (dma_issue<3, C, NT, SUB>(raw, nbytes, wb, e0, ne, win, w, lane, rows))
-    dma_fixup<3, C, SUB>(raw, nbytes, wb, e0, ne, win, w, lane, rows);
-  const float b = mine ? b_ld : 0.0f;
-  const int delta = mine ? (int)(w_ld & 14u) : 0;
-  if (EEGFX_GUARD && s == 0) gx[el * C + w] = guard_x2_int16(r, b);  // read after the barriers
-  dma_drain();
-  __syncthreads();
-
-  // samples 128 s + k of signal (epoch el, channel w): segment 2 s + k / 64, frame k % 64
-  const uint8_t* own = (const uint8_t*)(win + el * G::ESTR) + delta + 2 * col + 32 * G::SEGQ * s;
-  double a6[2], d6[2];
-  dwt8_toom6_cascade(
-      [&](int k) { return (int)*(const int16_t*)(own + 16 * G::SEGQ * (k >> 6) + G::FB * (k & 63)); },
-      r, b, lane & ~(LPS - 1), s, a6, d6);
-
-  const double q = group4_sum(__builtin_fma(
-      a6[0], a6[0], __builtin_fma(a6[1], a6[1], __builtin_fma(d6[0], d6[0], d6[1] * d6[1]))));
-  if (s == 0) part[el * C + w] = q;
-  __syncthreads();
-  const double acc = (part[el * C] + part[el * C + 1]) + part[el * C + 2];
-  bool fails = false;
-  if (EEGFX_GUARD && guard.total && s == 0 && mine)
-    fails = guard_fails(acc, kGuardK2Toom6, (gx[el * C] + gx[el * C + 1]) + gx[el * C + 2]);
-  const uint64_t flagged = __ballot(fails);  // bit 4e; the same mask in every channel wave
-  uint64_t left = 0;
-  if (flagged) {  // uniform over the workgroup, rare
-    int row;
-    const double x2 = channel_x2_rows<G::FB, G::SEGQ, G::ESTR * 4, SUB, LPS>(
-        flagged, (const uint8_t*)win, col, r, b, delta, lane, &row);
-    if (row >= 0) xs[row * C + w] = x2;
+  } else {
+    // EXACT: the rows go to LDS over the windows, and wave 0 normalises them in the reference's
+    // order (sequential sum of squares, sqrt, divide) and stores them
+    double* fb = (double*)win;
+    __syncthreads();  // every wave has read its samples: the rows may overwrite the window
+    // the row slot is recomputed here from an opaque copy of the lane id, so its address is not
+    // kept live across the filter bank (it was the one spilled VGPR)
+    int l2 = lane;
+    asm volatile("" : "+v"(l2));
+    const int slot = (l2 >> 3) * F + w * 16 + (l2 & 7);
+    fb[slot] = a6;
+    fb[slot + 8] = d6;
     __syncthreads();
-    bool f2 = false;
-    if (s == 0 && ((flagged >> (LPS * el)) & 1ull))
-      f2 = guard_fails(acc, kGuardK2Toom6,
-                       ((xs[el * C] + xs[el * C + 1]) + xs[el * C + 2]) * (1.0 + 0x1p-20));
-    left = __ballot(f2);
-    if (w == 0 && lane == 0) {
-      guard_count_rechecked(guard, __popcll(flagged));
-      if (left) guard_count_recomputed(guard, (unsigned long long)__popcll(left));
-    }
-  }
-  const double inv = rsqrt_nr1(acc);
-  if (mine && !((left >> (LPS * el)) & 1ull)) {
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    f64x2* o = (f64x2*)(out + (e0 + el) * F + w * 16 + 2 * s);
-    __builtin_nontemporal_store(f64x2{a6[0] * inv, a6[1] * inv}, o);
-    __builtin_nontemporal_store(f64x2{d6[0] * inv, d6[1] * inv}, o + 4);
-  }
-  if (left && w == 0) {
-    // the guard's rare path: each such row recomputed under EXACT from the recording by wave 0,
-    // the staged windows as scratch (every wave is done with them: the barrier above)
-    double* scratch = (double*)win;
-    double* rowbuf = scratch + 768;
-    for (uint64_t f = left; f; f &= f - 1) {
-      const int e = (__ffsll((unsigned long long)f) - 1) / LPS;
-      const int64_t B = wb[e0 + e] & ~(int64_t)1;  // byte offset of the window
-      const int64_t f0 = B / G::FB;
-      dwt8_exact_row_wave(
-          [&](int c, int k) {
-            const float rc = sel.res[c], bc = base[(e0 + e) * C + c];
-            const float v = f0 + k < n_frames
-                                ? (float)*(const int16_t*)(raw + B + (int64_t)k * G::FB + 2 * sel.col[c])
-                                : 0.0f;
-            float y = v * rc;
-            y = y - bc;
-            return (double)y;
-          },
-          C, 16, scratch, rowbuf, lane);
-      for (int i = lane; i < F; i += 64) out[(e0 + e) * F + i] = rowbuf[i];
-      wave_sync();
-    }
+    if (w == 0) normalise_store<F, false>(fb, norm, out + e0 * F, ne, lane);
   }
 }
 
@@ -825,20 +643,9 @@ hipError_t launch_fused_window(hipStream_t st, const void* raw, int64_t n_frames
   const int64_t* words = (const int64_t*)((const uint8_t*)scratch + window_words_offset(n, C));
   (void)pos;  // read by launch_fused_baseline, which wrote the window words
   const bool nt = streaming_reads(n_frames, n, dev::kWin + 8);
-  if (fast && EEGFX_WIN4) {
-    const dim3 g4((unsigned)((n + dev::kSub4 - 1) / dev::kSub4));
-    if (nt)
-      hipLaunchKernelGGL((dev::window4_kernel<true>), g4, dim3(192), 0, st, (const uint8_t*)raw,
-                         n_frames, sel, words, bs, n, out, guard);
-    else
-      hipLaunchKernelGGL((dev::window4_kernel<false>), g4, dim3(192), 0, st, (const uint8_t*)raw,
-                         n_frames, sel, words, bs, n, out, guard);
-    return hipGetLastError();
-  }
-  constexpr int subs = EEGFX_WIN_SUBS;
-  const dim3 g((unsigned)((n + dev::kSub * subs - 1) / (dev::kSub * subs)));
-#define EEGFX_WIN(FA, NTV, TK)                                                               \
-  hipLaunchKernelGGL((dev::window_kernel<3, 3, FA, NTV, subs, TK>), g, dim3(192 * subs), 0, st, \
+  const dim3 g((unsigned)((n + dev::kSub - 1) / dev::kSub));
+#define EEGFX_WIN(FA, NTV, TK)                                                          \
+  hipLaunchKernelGGL((dev::window_kernel<3, 3, FA, NTV, TK>), g, dim3(192), 0, st,      \
                      (const uint8_t*)raw, n_frames, sel, words, bs, n, out, guard)
   const bool trk = EEGFX_TRACK_X != 0 && (EEGFX_TRACK_X == 2 || track) && guard.total;
   if (fast && trk) { if (nt) EEGFX_WIN(true, true, true); else EEGFX_WIN(true, false, true); }

@@ -27,6 +27,10 @@ import fma_bound  # noqa: E402
 import gen_taps  # noqa: E402
 
 GUARD_H = os.path.join(REPO, "eeg_dataanalysispackage_amd", "csrc", "guard.h")
+# the widest bound any variant on record needed (the six-point form of
+# tools/probes/history/six_point_*.patch): the reference recordings are held to it, not only to
+# the shipped forms' smaller constants
+K2_WIDEST_ON_RECORD = 2.16e-4
 
 
 def header_constant(name):
@@ -38,8 +42,7 @@ def header_constant(name):
 
 def test_guard_constants_match_derivation():
     c = fma_bound.constants()
-    for name, key in (("kGuardK2Collapsed", "collapsed_k2"), ("kGuardK2Cascade", "cascade_k2"),
-                      ("kGuardK2Toom6", "toom6_k2")):
+    for name, key in (("kGuardK2Collapsed", "collapsed_k2"), ("kGuardK2Cascade", "cascade_k2")):
         k2 = header_constant(name)
         assert c[key] <= k2 <= 1.02 * c[key], (name, k2, c[key])
 
@@ -133,7 +136,7 @@ def crude_ratio(raw, pos, measured=False, three_max=False):
 def test_reference_selections_certified_by_int16_bound():
     from eeg_dataanalysispackage_amd import brainvision as bv
     k2 = max(header_constant("kGuardK2Collapsed"), header_constant("kGuardK2Cascade"),
-             header_constant("kGuardK2Toom6"))
+             K2_WIDEST_ON_RECORD)
     for base, guessed in ((DOD01, 1), (DOD02, 4)):
         raw = bv.read_raw(base + ".vhdr", base + ".eeg")
         pos, _, _ = bv.plan_markers(bv.read_markers(base + ".vmrk"), raw.shape[0], guessed)
@@ -147,7 +150,6 @@ def test_reference_selections_certified_by_int16_bound():
     assert flat
     r = crude_ratio(raw, flat[:2])
     assert np.all(r * r < header_constant("kGuardK2Collapsed"))
-    assert np.all(r * r < header_constant("kGuardK2Toom6"))
 
 
 def test_flat_windows_certified_by_the_second_stage():
@@ -155,7 +157,7 @@ def test_flat_windows_certified_by_the_second_stage():
     stage, the row's measured max |x| per channel: the device recomputes none of them (asserted
     on the GPU by test_gpu_guard.py), while null-space windows still fail it."""
     from eeg_dataanalysispackage_amd import brainvision as bv
-    k2 = max(header_constant("kGuardK2Collapsed"), header_constant("kGuardK2Toom6"))
+    k2 = max(header_constant("kGuardK2Collapsed"), K2_WIDEST_ON_RECORD)
     raw = bv.read_raw(DOD01 + ".vhdr", DOD01 + ".eeg")
     allpos = [m.position for m in bv.read_markers(DOD01 + ".vmrk") if m.position >= 100]
     crude = crude_ratio(raw, allpos)

@@ -6,6 +6,7 @@
 # ("# base: patch:<name>.patch").
 #   bash tools/probes/restore_variant.sh persistent_r02_pq2_fused [out.hip]
 #   then build it like an ablation: hipcc ... -DFUSED_SRC='"<dir>/fused.hip"' window_probe.hip
+# Without an output path the file is written to build/<name>/ under the base file's own name.
 set -euo pipefail
 HERE=$(cd "$(dirname "$0")" && pwd)
 restore() {  # restore <name> <out>
@@ -22,8 +23,14 @@ restore() {  # restore <name> <out>
   tail -n +2 "$p" | patch -s -o "$2" "$tmp"
   rm -f "$tmp"
 }
+base_file() {  # base_file <name>: the product file at the bottom of the patch's chain
+  local base
+  base=$(head -1 "$HERE/history/$1.patch" | sed 's/^# base: //')
+  if [[ "$base" == patch:* ]]; then base_file "$(basename "${base#patch:}" .patch)"
+  else basename "${base#*:}"; fi
+}
 name=$1
-out=${2:-$HERE/build/$name/$(echo "$name" | sed -E 's/.*_(fused|wide)$/\1/').hip}
+out=${2:-$HERE/build/$name/$(base_file "$name")}
 mkdir -p "$(dirname "$out")"
 restore "$name" "$out"
 echo "$out"

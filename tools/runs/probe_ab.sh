@@ -1,6 +1,6 @@
 #!/bin/bash
 # Interleaved A/B of window_probe builds (tools/probes/window_probe.hip) on one box.
-#   TAG=r06b VARIANTS="base:;b64:-DEEGFX_LDS_B64=1" MODES="PROBE_STEP=1;" REPS=3 bash tools/runs/probe_ab.sh
+#   TAG=ab VARIANTS="base:;scan:-DEEGFX_TRACK_X=0" MODES="PROBE_STEP=1;" REPS=3 bash tools/runs/probe_ab.sh
 # VARIANTS: name:defines pairs separated by ';' (each built against the product sources with the
 # defines); MODES: probe environments separated by ';' (empty = the window kernel alone).
 # Output: gpurun_out/$TAG/ab.log (one line per run).
