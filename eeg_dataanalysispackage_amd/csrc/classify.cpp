@@ -1,0 +1,236 @@
+// classify.cpp -- the MLlib classifier drivers of the eegfx C ABI (eegfx_logreg_*, eegfx_svm_*,
+// eegfx_spark_sample) over the kernels of logreg.hip.
+#include <sched.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "ctx.h"
+#include "spark_sample.h"
+
+// The processors this process may run on, as the JVM's Runtime.availableProcessors() counts them
+// (Spark local[*]'s defaultParallelism, SparkInitializer.java:44): the affinity mask, capped by a
+// cgroup CPU quota (cgroup v2 cpu.max or v1 cfs_quota_us / cfs_period_us), at least 1.
+// std::thread::hardware_concurrency() counts every online CPU of the machine instead.
+static int available_processors() {
+  int n = 0;
+  cpu_set_t set;
+  if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);
+  if (n < 1) n = (int)std::max(1u, std::thread::hardware_concurrency());
+  auto cap = [&](double quota, double period) {
+    if (quota > 0 && period > 0) n = std::min(n, std::max(1, (int)std::ceil(quota / period)));
+  };
+  if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
+    char q[32] = {0};
+    double period = 0;
+    if (fscanf(f, "%31s %lf", q, &period) == 2 && strcmp(q, "max") != 0) cap(atof(q), period);
+    fclose(f);
+  } else if (FILE* fq = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
+    double quota = -1, period = 0;
+    if (fscanf(fq, "%lf", &quota) != 1) quota = -1;
+    fclose(fq);
+    if (FILE* fp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
+      if (fscanf(fp, "%lf", &period) != 1) period = 0;
+      fclose(fp);
+    }
+    cap(quota, period);
+  }
+  return n;
+}
+
+// the classifier of LogisticRegressionClassifier.java:85-114 on the GPU
+// (csrc/logreg.hip): MLlib 1.6.2 LogisticRegressionWithSGD.  miniBatchFraction < 1: iteration i
+// trains on data.sample(false, f, 42 + i) of the rows in `num_partitions` ParallelCollectionRDD
+// slices (spark_sample.h), drawn on the host (threads over iterations) as one bit mask per
+// iteration and uploaded before the iterations that read them.  The hinge loop of
+// eegfx_ext.h (SVMWithSGD) stays full-batch (outside the contract, not extended).
+static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double* y, int64_t n,
+                         int32_t d, int32_t num_iterations, double step_size, double reg_param,
+                         double mini_batch_fraction, double convergence_tol,
+                         int32_t num_partitions, double* weights, int32_t* iterations_run,
+                         int mem) {
+  return guarded([&] {
+    if (!ctx || !weights) fail(EEGFX_EINVAL, "null argument");
+    check_mem(mem);
+    if (n < 1) fail(EEGFX_EINVAL, "empty training set");  // GeneralizedLinearAlgorithm: first()
+    if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
+    if (d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "d=%d outside [1, %d]", d, kLrMaxFeatures);
+    if (num_iterations < 0) fail(EEGFX_EINVAL, "num_iterations %d", num_iterations);
+    // RDD.sample's require(fraction >= 0.0), then BernoulliSampler's upper bound 1 up to
+    // RandomSampler.roundingEpsilon
+    if (!(mini_batch_fraction >= 0.0))
+      fail(EEGFX_EINVAL, "Negative fraction value: %g", mini_batch_fraction);
+    if (!(mini_batch_fraction <= 1.0 + 1e-6))
+      fail(EEGFX_EINVAL, "Sampling fraction (%g) must be on interval [0, 1]", mini_batch_fraction);
+    const bool sampled = mini_batch_fraction < 1.0;
+    if (sampled && grad != kGradLogistic)
+      fail(EEGFX_ENOTSUP, "miniBatchFraction %g: the SVM loop is full-batch only",
+           mini_batch_fraction);
+    if (sampled && num_partitions < 1) fail(EEGFX_EINVAL, "num_partitions %d", num_partitions);
+    ctx->activate();
+    const double* dX = X;
+    const double* dy = y;
+    if (mem == EEGFX_MEM_HOST) {
+      double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
+      double* by = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
+      HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice,
+                               ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(by, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice,
+                               ctx->stream));
+      dX = bx;
+      dy = by;
+    }
+    const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
+    std::vector<uint8_t> hs(sbytes, 0);
+    LrState* h = (LrState*)hs.data();
+    h->converged = num_iterations == 0 ? 1 : 0;
+    memcpy(h->w, weights, sizeof(double) * (size_t)d);  // initial weights (zeros in MLlib)
+    LrState* st = (LrState*)ctx->lr_state.get(sbytes);
+    HIP_CHECK(hipMemcpyAsync(st, hs.data(), sbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(launch_lr_validate(ctx->stream, dy, n, st));
+    const int G = lr_grid(n);
+    double* part = (double*)ctx->lr_part.get(sizeof(double) * (size_t)G * d);
+    if (!sampled) {
+      for (int i = 0; i < num_iterations; ++i)
+        HIP_CHECK(launch_lr_iteration(ctx->stream, grad, dX, dy, n, d, nullptr, n, st, part, G,
+                                      step_size, reg_param, convergence_tol, num_iterations));
+    } else {
+      // the masks of up to ~256 MB of iterations at a time, drawn by threads over iterations
+      const int64_t words = (n + 31) / 32;
+      const int chunk = (int)std::max<int64_t>(
+          1, std::min<int64_t>(num_iterations, ((int64_t)64 << 20) / words));
+      std::vector<uint32_t> masks((size_t)(chunk * words));
+      std::vector<int64_t> counts((size_t)chunk);
+      uint32_t* dmask = (uint32_t*)ctx->lr_mask.get(sizeof(uint32_t) * masks.size());
+      const int T_max = std::min(64, available_processors());
+      for (int i0 = 0; i0 < num_iterations; i0 += chunk) {
+        const int k = std::min(chunk, num_iterations - i0);
+        ctx->drain();  // the previous chunk's upload and iterations are done with both buffers
+        if (i0 > 0) {  // converged (or stopped): the remaining iterations would be skipped
+          int32_t conv = 0;
+          HIP_CHECK(hipMemcpyAsync(&conv, &st->converged, sizeof(conv), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+          HIP_CHECK(hipStreamSynchronize(ctx->stream));
+          if (conv != 0) break;
+        }
+        const int T = std::max(1, std::min(k, T_max));
+        {
+          Joiner pool;
+          for (int t = 0; t < T; ++t)
+            pool.th.emplace_back([&, t] {
+              for (int j = t; j < k; j += T)  // GradientDescent's i = i0 + j + 1, seed 42 + i
+                counts[j] = spark::sample_mask(n, mini_batch_fraction, num_partitions,
+                                               42 + (int64_t)(i0 + j + 1),
+                                               &masks[(size_t)j * words]);
+            });
+        }
+        HIP_CHECK(hipMemcpyAsync(dmask, masks.data(), sizeof(uint32_t) * (size_t)(k * words),
+                                 hipMemcpyHostToDevice, ctx->stream));
+        for (int j = 0; j < k; ++j)
+          HIP_CHECK(launch_lr_iteration(ctx->stream, grad, dX, dy, n, d, dmask + (size_t)j * words,
+                                        counts[j], st, part, G, step_size, reg_param,
+                                        convergence_tol, num_iterations));
+      }
+    }
+    HIP_CHECK(hipMemcpyAsync(hs.data(), st, sbytes, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->drain();
+    if (h->converged == 2) fail(EEGFX_EINVAL, "Input validation failed: labels must be 0.0 or 1.0");
+    memcpy(weights, h->w, sizeof(double) * (size_t)d);
+    if (iterations_run) *iterations_run = h->iter;
+  });
+}
+
+static int glm_predict(int grad, eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
+                       const double* weights, double intercept, double threshold, double* out,
+                       int mem) {
+  return guarded([&] {
+    if (!ctx || !weights) fail(EEGFX_EINVAL, "null argument");
+    check_mem(mem);
+    if (n < 0 || d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "n=%lld d=%d", (long long)n, d);
+    if (n == 0) return;
+    if (!X || !out) fail(EEGFX_EINVAL, "null X / out");
+    ctx->activate();
+    const double* dX = X;
+    double* dout = out;
+    if (mem == EEGFX_MEM_HOST) {
+      double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
+      HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice,
+                               ctx->stream));
+      dX = bx;
+      dout = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
+    }
+    const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
+    LrState* st = (LrState*)ctx->lr_state.get(sbytes);
+    HIP_CHECK(hipMemcpyAsync(st->w, weights, sizeof(double) * (size_t)d, hipMemcpyHostToDevice,
+                             ctx->stream));
+    const bool use_t = !std::isnan(threshold);  // clearThreshold -> scores / margins
+    HIP_CHECK(launch_lr_predict(ctx->stream, grad, dX, n, d, st->w, intercept, threshold,
+                                use_t ? 1 : 0, dout));
+    if (mem == EEGFX_MEM_HOST)
+      HIP_CHECK(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    ctx->drain();
+  });
+}
+
+extern "C" {
+
+int eegfx_logreg_sgd_train_partitioned(eegfx_ctx* ctx, const double* X, const double* y,
+                                       int64_t n, int32_t d, int32_t num_iterations,
+                                       double step_size, double reg_param,
+                                       double mini_batch_fraction, double convergence_tol,
+                                       int32_t num_partitions, double* weights,
+                                       int32_t* iterations_run, int mem) {
+  return glm_sgd_train(kGradLogistic, ctx, X, y, n, d, num_iterations, step_size, reg_param,
+                       mini_batch_fraction, convergence_tol, num_partitions, weights,
+                       iterations_run, mem);
+}
+
+int eegfx_logreg_sgd_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                           int32_t num_iterations, double step_size, double reg_param,
+                           double mini_batch_fraction, double convergence_tol, double* weights,
+                           int32_t* iterations_run, int mem) {
+  // Spark local[*] (SparkInitializer.java:44): defaultParallelism = the processors available
+  // to the process (Runtime.availableProcessors(): affinity and cgroup quota honoured)
+  return glm_sgd_train(kGradLogistic, ctx, X, y, n, d, num_iterations, step_size, reg_param,
+                       mini_batch_fraction, convergence_tol, (int32_t)available_processors(),
+                       weights, iterations_run, mem);
+}
+
+int eegfx_spark_sample(int64_t n, double fraction, int32_t num_partitions, int64_t seed,
+                       uint32_t* mask, int64_t* kept) {
+  return guarded([&] {
+    if (n < 0 || num_partitions < 1 || !mask || !kept) fail(EEGFX_EINVAL, "bad argument");
+    if (!(fraction >= -1e-6 && fraction <= 1.0 + 1e-6))
+      fail(EEGFX_EINVAL, "Sampling fraction (%g) must be on interval [0, 1]", fraction);
+    *kept = spark::sample_mask(n, fraction, num_partitions, seed, mask);
+  });
+}
+
+int eegfx_logreg_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
+                         const double* weights, double intercept, double threshold, double* out,
+                         int mem) {
+  return glm_predict(kGradLogistic, ctx, X, n, d, weights, intercept, threshold, out, mem);
+}
+
+// The classifier of SVMClassifier.java:83-111 (MLlib 1.6.2 SVMWithSGD: HingeGradient, the same
+// SquaredL2Updater / GradientDescent loop) and SVMModel.predict (:71, :114-137).
+int eegfx_svm_sgd_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                        int32_t num_iterations, double step_size, double reg_param,
+                        double mini_batch_fraction, double convergence_tol, double* weights,
+                        int32_t* iterations_run, int mem) {
+  return glm_sgd_train(kGradHinge, ctx, X, y, n, d, num_iterations, step_size, reg_param,
+                       mini_batch_fraction, convergence_tol, 1, weights, iterations_run, mem);
+}
+
+int eegfx_svm_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d, const double* weights,
+                      double intercept, double threshold, double* out, int mem) {
+  return glm_predict(kGradHinge, ctx, X, n, d, weights, intercept, threshold, out, mem);
+}
+
+}  // extern "C"

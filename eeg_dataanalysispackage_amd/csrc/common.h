@@ -51,7 +51,7 @@ int guarded(F&& f) {
   }
 }
 
-// ---- context accessors for the host sources that do not see ctx.h (api.cpp) -------------------
+// ---- context accessors for the host sources that do not see ctx.h (comm.cpp; api.cpp defines them)
 int ctx_device(const eegfx_ctx* ctx);
 void* ctx_stream(const eegfx_ctx* ctx);  // the context's hipStream_t
 

@@ -1,5 +1,7 @@
 // ctx.h -- the device context (struct eegfx_ctx) and the helpers that the host sources share:
-// what api.cpp defines and odp.cpp (the OffLineDataProvider) uses.  Internal: not installed.
+// the argument checks (defined in api.cpp) and the device-pointer pipelines (routes.cpp), used by
+// api.cpp, streamed.cpp, classify.cpp, mailbox.cpp and odp.cpp (the OffLineDataProvider).
+// Internal: not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,7 +18,7 @@
 #include "common.h"
 #include "eegfx_ext.h"
 #include "launch.h"
-
+#include "mailbox.h"
 
 #define HIP_CHECK(expr)                                                                 \
   do {                                                                                  \
@@ -257,99 +259,10 @@ struct eegfx_ctx {
     }
     HIP_CHECK(e);
   }
-  // The opt-in resident small-batch server (eegfx_ctx_set_mailbox, features_mailbox_kernel): a
-  // host-mapped command block, the kernel's own stream (never the context stream: the kernel
-  // stays resident), the request sequence and the time of the last request.  A server needs a
-  // hardware queue of its own (a queue runs its packets in order: a second kernel behind a
-  // resident one waits for it to idle out), and the highest-priority pool has kMbSlotsPerDevice of
-  // them, so at most that many contexts of the process hold a server slot on a device
-  // (mb_acquire); the others serve their calls on the launch path, and take a slot when one frees.
-  bool mailbox = false;   // enabled by the caller
-  bool mb_slot = false;   // holds one of the device's server slots
-  hipStream_t mb_stream = nullptr;
-  MailboxCmd* mb_host = nullptr;
-  MailboxCmd* mb_dev = nullptr;
-  size_t mb_cap = 0;  // pinned_pool capacity of mb_host
-  uint32_t mb_seq = 0;
-  uint32_t mb_gen = 0;      // launch generation (MailboxCmd::alive)
-  bool mb_live = false;     // launched and not stopped by the host (it may still have idled out)
-  bool mb_started = false;  // the live server has published its generation
-  bool mb_stuck = false;    // a server that did not start in time: stopped, not yet returned
-  std::chrono::steady_clock::time_point mb_last{};
-  static constexpr uint64_t kMbIdleTicks = 100000000;  // 1 s of s_memrealtime (100 MHz)
-  void mb_launch() {
-    // the staging a server reads is fixed for its lifetime (growing it stops the server first)
-    mb_host->rows = pin_in.p ? (const double*)pin_in.device_ptr() : nullptr;
-    mb_host->out = pin_out.p ? (double*)pin_out.device_ptr() : nullptr;
-    if (++mb_gen == 0) mb_gen = 1;
-    HIP_CHECK(launch_features_mailbox(mb_stream, mb_dev, kMbIdleTicks, mb_gen));
-    mb_live = true;
-    mb_started = false;
-  }
-  // Stops a live server: `stop` is seen within one poll.  A server that has not returned after
-  // 10 s (100 ms if it has not been seen to start: its queue is held by another resident kernel)
-  // keeps `stop` set, so it returns as soon as it runs, and is marked stuck; mb_ready clears
-  // `stop` once it has returned.
-  // Returns whether the kernel has returned.
-  bool mb_stop() {
-    if (!mb_host || !mb_live) return true;
-    __atomic_store_n(&mb_host->stop, 1u, __ATOMIC_RELEASE);
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t q;
-    while ((q = hipStreamQuery(mb_stream)) == hipErrorNotReady) {
-      if (std::chrono::steady_clock::now() - t0 >
-          (mb_started ? std::chrono::milliseconds(10000) : std::chrono::milliseconds(100))) {
-        mb_live = false;
-        mb_stuck = true;
-        return false;
-      }
-      std::this_thread::yield();
-    }
-    __atomic_store_n(&mb_host->stop, 0u, __ATOMIC_RELEASE);
-    mb_live = false;
-    HIP_CHECK(q);
-    return true;
-  }
-  // hipSuccess: the server kernel has returned; hipErrorNotReady: it is running; anything else
-  // is an error of the stream and is raised
-  bool mb_returned() {
-    const hipError_t q = hipStreamQuery(mb_stream);
-    if (q == hipErrorNotReady) return false;
-    HIP_CHECK(q);
-    return true;
-  }
-  // Whether the resident server takes this call (false: the launch path).  Takes a device slot
-  // and sets the server up on first use; restarts a server that may be near its 1 s idle exit
-  // (no request for 500 ms) so a request never races that exit; posts nothing until the server
-  // has published its generation, and falls back to the launch path (marking the server stuck)
-  // if it has not started within kMbStartWait.
-  static constexpr auto kMbStartWait = std::chrono::milliseconds(20);
-  bool mb_ready();
-  // One request: n epochs of packed window rows in pin_in -> rows in pin_out (after mb_ready).
-  void mb_serve(int64_t n, int C, int nfeat) {
-    MailboxCmd* m = mb_host;
-    if (++mb_seq == 0) mb_seq = 1;  // 0 means "no request" to the kernel
-    const auto now = std::chrono::steady_clock::now();
-    __atomic_store_n(&m->req, mailbox_request(mb_seq, C, nfeat, n), __ATOMIC_RELEASE);
-    for (uint64_t spin = 1;; ++spin) {
-      if (__atomic_load_n(&m->done, __ATOMIC_ACQUIRE) == mb_seq) break;
-      // as wait_small: a waiter past kSmallSpin sleeps between polls instead of staying runnable
-      if ((spin & 63) == 0 && std::chrono::steady_clock::now() - now > kSmallSpin)
-        std::this_thread::sleep_for(std::chrono::microseconds(10));
-      if ((spin & 4095) == 0) {
-        // a server that returned with the request pending (an error, or a stop from another
-        // path): serve it again on the same stream, after that kernel
-        if (mb_returned() && __atomic_load_n(&m->done, __ATOMIC_ACQUIRE) != mb_seq) mb_launch();
-        if (std::chrono::steady_clock::now() - now > std::chrono::seconds(30))
-          fail(EEGFX_EHIP, "mailbox request %u not served within 30 s", mb_seq);
-      }
-      __builtin_ia32_pause();
-    }
-    mb_last = std::chrono::steady_clock::now();
-  }
-  void release_mailbox();
+  // The opt-in resident small-batch server (eegfx_ctx_set_mailbox): mailbox.h.
+  Mailbox mb{this};
   void release_stream_resources() {
-    release_mailbox();
+    mb.release();
     if (small_done) (void)hipEventDestroy(small_done);
     small_done = nullptr;
     for (hipEvent_t e : copied) (void)hipEventDestroy(e);
@@ -413,6 +326,17 @@ struct eegfx_ctx {
 
 namespace eegfx {
 
+void check_mem(int mem);
+// The raw entries' argument ladder up to the null-buffer check (api.cpp check_raw_args goes on
+// from it).  `mem`: EEGFX_MEM_HOST from an entry without a mem flag.
+void check_raw_head(const eegfx_ctx* ctx, int mem, const void* raw, int fmt, int64_t n_frames,
+                    int ct, const int64_t* pos, int64_t n, const void* out);
+
+// raw -> features on the context stream (device pointers).  Fused kernel when one covers the
+// layout, otherwise cut + features through the context scratch buffer.
+void run_features_from_raw(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n_frames, int ct,
+                           const ChanSel& sel, int C, const int64_t* pos, int64_t n, double* out);
+
 // raw -> epochs + features (device pointers): the one-pass kernels when the layout fits them,
 // else the cut pass followed by the batch extract over the rows it wrote.  E: double or float epochs
 // (eegfx_process_recording_epochs / _f32): the same kernels, the same rows in `feat`.
@@ -420,5 +344,15 @@ template <typename E>
 void run_epochs_and_features(eegfx_ctx* ctx, const void* raw, int fmt, int64_t n_frames, int ct,
                              const ChanSel& sel, int C, const int64_t* pos, int64_t n, E* ep,
                              double* feat);
+
+// Epoch rows (device pointers, `row_stride` elements apart, double or float) -> features: the
+// library's one choice between the full-pyramid kernels (feature sizes past a6 ++ d6: no guard)
+// and the filter bank under the fma guard.  The guard is taken for these n rows
+// (eegfx_ctx::guard_for, once per launch) unless the caller took one for a whole call that it
+// launches in chunks (`call_guard`).  No tic / toc: the callers bracket what they time.
+template <typename E>
+void run_features_from_epochs(eegfx_ctx* ctx, const E* ep, int64_t n, int C, int skip,
+                              int feature_size, double* out, int row_stride,
+                              const Guard* call_guard = nullptr);
 
 }  // namespace eegfx

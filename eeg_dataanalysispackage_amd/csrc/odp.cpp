@@ -543,15 +543,8 @@ int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int
         return;
       }
       double* d_out = (double*)ctx->out.get(bytes);
-      if (wide_features(feature_size)) {
-        HIP_CHECK(launch_pyramid_from_epochs(ctx->stream, (const double*)s.d_epochs, s.count, 3,
-                                             skip, feature_size, d_out, EEGFX_POSTSTIMULUS));
-      } else {
-        const Guard g = ctx->guard_for(s.count);
-        HIP_CHECK(launch_features_from_epochs(ctx->stream, (const double*)s.d_epochs, s.count, 3,
-                                              skip, feature_size, ctx->numerics != EEGFX_EXACT,
-                                              d_out, EEGFX_POSTSTIMULUS, g));
-      }
+      run_features_from_epochs(ctx, (const double*)s.d_epochs, s.count, 3, skip, feature_size,
+                               d_out, EEGFX_POSTSTIMULUS);
       HIP_CHECK(hipMemcpyAsync(dst, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     });
   });
