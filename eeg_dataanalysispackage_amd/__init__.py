@@ -5,17 +5,21 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
 * :class:`OffLineDataProvider` -- DataTransformation/OffLineDataProvider.java
 * :class:`IFeatureExtraction`, :class:`WaveletTransform` -- FeatureExtraction/*.java (fe=dwt-8)
 * :class:`Context` -- device/stream + the batched and fused compute entry points
+* :class:`DecisionTreeClassifier`, :func:`dtree_train`, :func:`dtree_predict` -- train_clf=dt
+  (the other classifiers live in :mod:`classification`)
 * :mod:`brainvision` -- native .vhdr/.vmrk reader and marker planner
 """
 from ._lib import EegfxError, LIB_PATH, lib
 from .brainvision import (ChannelInfo, EEGMarker, Header, plan_markers, read_header,
                           read_markers, read_raw, recording_frames)
+from .classification import DecisionTreeClassifier, dtree_predict, dtree_train
 from .context import Context, device_count
 from .data_provider import OffLineDataProvider
 from .feature_extraction import IFeatureExtraction, WaveletTransform
 
 __all__ = [
-    "Context", "ChannelInfo", "EEGMarker", "EegfxError", "Header", "IFeatureExtraction",
-    "LIB_PATH", "OffLineDataProvider", "WaveletTransform", "device_count", "lib",
+    "Context", "ChannelInfo", "DecisionTreeClassifier", "EEGMarker", "EegfxError", "Header",
+    "IFeatureExtraction", "LIB_PATH", "OffLineDataProvider", "WaveletTransform", "device_count",
+    "dtree_predict", "dtree_train", "lib",
     "plan_markers", "read_header", "read_markers", "read_raw", "recording_frames",
 ]

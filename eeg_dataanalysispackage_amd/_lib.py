@@ -70,6 +70,13 @@ class OdpShard(Structure):
 
 
 ODP_MAX_SHARDS = 64
+GINI, ENTROPY = 0, 1
+
+
+class TreeNode(Structure):
+    _fields_ = [("id", c_int32), ("feature", c_int32), ("left", c_int32), ("right", c_int32),
+                ("threshold", c_double), ("predict", c_double), ("impurity", c_double),
+                ("gain", c_double)]
 
 
 class EegfxError(RuntimeError):
@@ -136,6 +143,11 @@ SIGNATURES = {
                                    POINTER(c_int64)]),
     "eegfx_logreg_predict": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_double,
                                      c_double, c_void_p, c_int]),
+    "eegfx_dtree_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                  c_int32, c_int32, c_int64, c_void_p, c_int32, POINTER(c_int32),
+                                  c_int]),
+    "eegfx_dtree_predict": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32,
+                                    c_void_p, c_int]),
     "eegfx_svm_sgd_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                     c_double, c_double, c_double, c_double, c_void_p,
                                     POINTER(c_int32), c_int]),

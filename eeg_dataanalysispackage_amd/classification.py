@@ -9,6 +9,8 @@ MLlib 1.6.2 ``LogisticRegressionWithSGD`` on the device (``eegfx_logreg_sgd_trai
 including the reference's reading of the column-major confusion matrix (its "false positives"
 count actual-1 / predicted-0).  ``SVMClassifier`` is the same flow with MLlib 1.6.2
 ``SVMWithSGD`` (HingeGradient, ``eegfx_svm_sgd_train``) and ``SVMModel.predict`` (margin > 0).
+``DecisionTreeClassifier`` (train_clf=dt) is the flow again with MLlib 1.6.2 ``DecisionTree``
+(``eegfx_dtree_train`` / ``eegfx_dtree_predict``).
 Model save/load (Spark model directories) is out of scope.
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
 from ._lib import EegfxError, lib, ptr
 from .context import Context, _contig, _is_device, _mem
 
@@ -120,6 +123,65 @@ def svm_predict(ctx: Context, X, weights, intercept: float = 0.0,
     """SVMModel.predict on the device: margin w.x + b > threshold (0.0) -> 1 else 0, or the
     margin when ``threshold`` is None (clearThreshold)."""
     return _predict("eegfx_svm_predict", ctx, X, weights, intercept, threshold)
+
+
+# Strategy.defaultStrategy("Classification") (MLlib 1.6.2)
+DEFAULT_IMPURITY = "gini"
+DEFAULT_MAX_DEPTH = 5
+DEFAULT_MAX_BINS = 32
+DEFAULT_MIN_INSTANCES_PER_NODE = 1
+TREE_NODE = np.dtype(_lib.TreeNode)
+
+
+def dtree_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
+                max_depth: int = DEFAULT_MAX_DEPTH, max_bins: int = DEFAULT_MAX_BINS,
+                min_instances_per_node: int = DEFAULT_MIN_INSTANCES_PER_NODE,
+                split_seed: int = 0) -> np.ndarray:
+    """MLlib 1.6.2 DecisionTree (two classes, continuous features) on the device
+    (eegfx_dtree_train); returns the nodes, ascending by Spark's node index, as a structured
+    array (id, feature, left, right, threshold, predict, impurity, gain; a leaf has feature -1).
+    X (n x d float64, host numpy or device torch) and y (n labels 0/1) may live on either side.
+    impurity: "gini" or "entropy".  split_seed seeds the Bernoulli sample of the rows the
+    thresholds come from when n > max(max_bins^2, 10000) (Spark draws it fresh on every run)."""
+    kinds = {"gini": _lib.GINI, "entropy": _lib.ENTROPY}
+    if impurity not in kinds:
+        raise ValueError(f"impurity must be one of {sorted(kinds)}, got {impurity!r}")
+    if _is_device(X) != _is_device(y):
+        raise ValueError("X and y must both be host or both be device arrays")
+    X = _contig(X, np.float64)
+    y = _contig(y, np.float64)
+    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
+        raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
+    n, d = int(X.shape[0]), int(X.shape[1])
+    # every leaf holds a row and no node lies below max_depth
+    depth = min(max(int(max_depth), 0), 30)
+    capacity = max(1, min(2 ** (depth + 1) - 1, 2 * n - 1))
+    nodes = np.zeros(capacity, dtype=TREE_NODE)
+    count = c_int32()
+    mem = _mem(X, y)
+    ctx._call(mem, X, lib().eegfx_dtree_train, ctx.handle, ptr(X), ptr(y), n, d, kinds[impurity],
+              int(max_depth), int(max_bins), int(min_instances_per_node), int(split_seed),
+              ptr(nodes), capacity, byref(count), mem)
+    return nodes[:count.value].copy()
+
+
+def dtree_predict(ctx: Context, X, nodes):
+    """DecisionTreeModel.predict on the device (eegfx_dtree_predict): the 0/1 of the leaf each row
+    of X (host numpy or device torch) reaches; left iff x[feature] <= threshold."""
+    nodes = np.ascontiguousarray(nodes, dtype=TREE_NODE)
+    X = _contig(X, np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if _is_device(X):
+        import torch
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    else:
+        out = np.empty(n, dtype=np.float64)
+    mem = _mem(X, out)
+    ctx._call(mem, X, lib().eegfx_dtree_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
+              int(nodes.shape[0]), ptr(out), mem)
+    return out
 
 
 class ClassificationStatistics:
@@ -265,5 +327,48 @@ class SVMClassifier(LogisticRegressionClassifier):
         return svm_predict(self.context, features, self.weights)
 
 
-__all__ = ["ClassificationStatistics", "LogisticRegressionClassifier", "SVMClassifier", "predict",
-           "reference_statistics", "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]
+class DecisionTreeClassifier(LogisticRegressionClassifier):
+    """IClassifier for train_clf=dt (DecisionTreeClassifier.java), GPU-resident: the flow of
+    LogisticRegressionClassifier with MLlib's DecisionTree and DecisionTreeModel.predict."""
+
+    def __init__(self, context: Optional[Context] = None):
+        super().__init__(context)
+        self.nodes: Optional[np.ndarray] = None
+        # seed of the threshold sample of more than max(max_bins^2, 10000) rows
+        self.split_seed = 0
+
+    def train(self, epochs, targets: Sequence[float], fe) -> None:
+        """:85-127 -- Strategy.defaultStrategy("Classification") (Gini, depth 5, 32 bins, 1
+        instance per node); with config_max_bins / config_impurity / config_max_depth /
+        config_min_instances_per_node all set, those instead ("gini" is Gini, any other string
+        Entropy)."""
+        self.fe = fe
+        X = self._features(epochs)
+        y = np.asarray(targets, dtype=np.float64)
+        c = self.config
+        if all(k in c for k in ("config_max_bins", "config_impurity", "config_max_depth",
+                                "config_min_instances_per_node")):
+            self.nodes = dtree_train(
+                self.context, X, y,
+                impurity="gini" if c["config_impurity"] == "gini" else "entropy",
+                max_depth=int(c["config_max_depth"]), max_bins=int(c["config_max_bins"]),
+                min_instances_per_node=int(c["config_min_instances_per_node"]),
+                split_seed=self.split_seed)
+        else:
+            self.nodes = dtree_train(self.context, X, y, split_seed=self.split_seed)
+
+    def predict(self, features) -> np.ndarray:
+        if self.nodes is None:
+            raise RuntimeError("The classifier has not been trained")  # IllegalStateException
+        return dtree_predict(self.context, features, self.nodes)
+
+    def test(self, epochs, targets: Sequence[float]) -> ClassificationStatistics:
+        if self.nodes is None:
+            raise RuntimeError("The classifier has not been trained")
+        pred = self.predict(self._features(epochs))
+        return reference_statistics(pred, targets)
+
+
+__all__ = ["ClassificationStatistics", "DecisionTreeClassifier", "LogisticRegressionClassifier",
+           "SVMClassifier", "dtree_predict", "dtree_train", "predict", "reference_statistics",
+           "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]

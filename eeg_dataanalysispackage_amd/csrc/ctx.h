@@ -175,6 +175,9 @@ struct eegfx_ctx {
   size_t n_timed = 0;
   DevBuf raw, pos, out, scratch, fused;
   DevBuf lr_x, lr_y, lr_state, lr_part, lr_mask;  // logistic regression (eegfx_logreg_*)
+  // the decision tree (eegfx_dtree_*): threshold table, bins, slot + label per row, one group's
+  // histograms (and the gathered split sample), a level's decisions / the nodes of a prediction
+  DevBuf dt_tab, dt_bins, dt_rows, dt_hist, dt_dec;
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
   PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
                                          // a sharded provider's worker: the file spans it reads
@@ -203,12 +206,12 @@ struct eegfx_ctx {
   }
   void bind_buffers() {
     for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list})
+                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec})
       b->sp = &stream;
   }
   void release_buffers() {
     for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list})
+                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec})
       b->release();
     pin_in.release();
     pin_out.release();

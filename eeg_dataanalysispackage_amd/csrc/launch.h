@@ -180,4 +180,37 @@ hipError_t launch_lr_predict(hipStream_t st, int grad, const double* X, int64_t 
                              const double* w, double intercept, double threshold,
                              int use_threshold, double* out);
 
+
+// dtree.hip: the O(n d) passes of the decision tree (eegfx_dtree_*; the host half is dtree_host.h).
+struct DtDecision {   // one active node's outcome of a level, read by dt_route_kernel
+  int32_t feature;    // -1: the node became a leaf
+  int32_t split;      // bins 0..split go left
+  int32_t left, right;  // the children's slots of the next level, -1: leaf
+};
+struct DtNode {       // one node as dt_predict_kernel walks it
+  int32_t feature, left, right, pad;
+  double threshold, predict;
+};
+constexpr int kDtMaxBins = 256;
+// counters (uint32) of the histogram kernel's LDS: 128 KB of a gfx950 CU's 160 KB
+constexpr int kDtLdsCounters = 32768;
+// X -> bins uint8 [n][d] (the thresholds below the value, of feature f's nthr[f] ascending ones at
+// thr[f * T]), label uint8 [n], slot int32 [n] = 0.  flags[0] = 1: a non-finite feature;
+// flags[1] = 1: a label other than 0.0 / 1.0 (both zeroed by the caller).
+hipError_t launch_dt_bin(hipStream_t st, const double* X, const double* y, int64_t n, int d,
+                         int T, const int32_t* nthr, const double* thr, int32_t* flags,
+                         uint8_t* bins, uint8_t* label, int32_t* slot);
+// hist uint32 [g][d][B][2] (zeroed by the caller) += the rows whose slot lies in [g0, g0 + g);
+// privatised in LDS when g * d * B * 2 <= kDtLdsCounters, else global atomics
+hipError_t launch_dt_hist(hipStream_t st, const uint8_t* bins, const uint8_t* label,
+                          const int32_t* slot, int64_t n, int d, int B, int g0, int g,
+                          uint32_t* hist);
+hipError_t launch_dt_route(hipStream_t st, const uint8_t* bins, int64_t n, int d,
+                           const DtDecision* dec, int32_t* slot);
+// rows idx[0..m) of X, packed
+hipError_t launch_dt_gather(hipStream_t st, const double* X, int d, const int64_t* idx, int64_t m,
+                            double* out);
+hipError_t launch_dt_predict(hipStream_t st, const double* X, int64_t n, int d,
+                             const DtNode* nodes, int n_nodes, double* out);
+
 }  // namespace eegfx

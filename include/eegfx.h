@@ -26,8 +26,9 @@
  * in [0, n_frames]); a violation is reported as EEGFX_ERANGE by the next call on that context
  * that synchronises it, which also clears it.  The calls that synchronise are
  * eegfx_ctx_synchronize, eegfx_ctx_guard_stats / _detail, every EEGFX_MEM_HOST compute call,
- * eegfx_read_raw with EEGFX_MEM_DEVICE, eegfx_logreg_sgd_train / eegfx_svm_sgd_train, and
- * eegfx_logreg_predict / eegfx_svm_predict with EEGFX_MEM_DEVICE.  When such a call returns
+ * eegfx_read_raw with EEGFX_MEM_DEVICE, eegfx_logreg_sgd_train / eegfx_svm_sgd_train /
+ * eegfx_dtree_train, and eegfx_logreg_predict / eegfx_svm_predict / eegfx_dtree_predict with
+ * EEGFX_MEM_DEVICE.  When such a call returns
  * EEGFX_ERANGE for an earlier call's position, its own work has completed and its outputs are
  * valid; the rows of the epochs with the refused positions are unspecified.  Results of
  * EEGFX_MEM_DEVICE calls are unspecified until a synchronising call has returned EEGFX_OK.  Host
@@ -372,6 +373,37 @@ int eegfx_logreg_sgd_train_partitioned(eegfx_ctx* ctx, const double* X, const do
  * mask = bit r of word r / 32 set for every kept row ((n + 31) / 32 words), *kept = their count. */
 int eegfx_spark_sample(int64_t n, double fraction, int32_t num_partitions, int64_t seed,
                        uint32_t* mask, int64_t* kept);
+
+/* ---- train_clf=dt: the decision tree (DecisionTreeClassifier.java:99-127) --------------------
+ * MLlib 1.6.2 DecisionTree over continuous features and two classes, as DESIGN.md section 10
+ * states it: per-feature thresholds from min(n, max(max_bins^2, 10000)) sampled rows (all rows, or
+ * RDD.sample(false, required / n, split_seed) in one partition), rows binned on the device, one
+ * integer class histogram per node and level, the best split chosen on the host, rows routed to
+ * their children on the device.  The statistics are integer counts and every gain is plain fp64,
+ * so the tree is defined bit for bit.  eegfx_dtree_train writes the nodes ascending by `id` into
+ * the host array `nodes`; when `capacity` is too small it returns EEGFX_EINVAL with the count
+ * needed in *n_nodes.  Limits: 1 <= d <= 1024, 2 <= max_bins <= 256 (above: EEGFX_ENOTSUP),
+ * 0 <= max_depth <= 30, min_instances_per_node >= 1, 2 <= n < 2^31.  A non-finite feature or a
+ * label other than 0.0 / 1.0 is EEGFX_EINVAL.  eegfx_dtree_predict walks the tree per row (left
+ * iff x[feature] <= threshold, so a NaN goes right) and writes the leaf's `predict`; a node array
+ * whose children do not lie inside the array and after their parent, or with a feature >= d, is
+ * EEGFX_EINVAL.  `mem` covers X, y and out; both calls synchronise. */
+#define EEGFX_GINI 0
+#define EEGFX_ENTROPY 1
+typedef struct {
+  int32_t id;            /* Spark node index: root 1, children 2i and 2i + 1 */
+  int32_t feature;       /* -1: leaf */
+  int32_t left, right;   /* array positions of the children, -1: leaf */
+  double threshold, predict, impurity, gain;
+} eegfx_tree_node;
+int eegfx_dtree_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                      int32_t impurity, int32_t max_depth, int32_t max_bins,
+                      int32_t min_instances_per_node, int64_t split_seed,
+                      eegfx_tree_node* nodes /* host */, int32_t capacity, int32_t* n_nodes,
+                      int mem);
+int eegfx_dtree_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
+                        const eegfx_tree_node* nodes /* host */, int32_t n_nodes, double* out,
+                        int mem);
 
 /* eegfx_svm_* (MLlib SVMWithSGD on the same device loop) is declared in eegfx_ext.h: SURVEY.md
  * section 2 marks the SVM classifier out of the hot-path scope, so it is not part of this contract. */
