@@ -6,20 +6,24 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
 * :class:`IFeatureExtraction`, :class:`WaveletTransform` -- FeatureExtraction/*.java (fe=dwt-8)
 * :class:`Context` -- device/stream + the batched and fused compute entry points
 * :class:`DecisionTreeClassifier`, :func:`dtree_train`, :func:`dtree_predict` -- train_clf=dt
+* :class:`RandomForestClassifier`, :func:`rforest_train`, :func:`rforest_predict`,
+  :func:`poisson_bag` -- train_clf=rf
   (the other classifiers live in :mod:`classification`)
 * :mod:`brainvision` -- native .vhdr/.vmrk reader and marker planner
 """
 from ._lib import EegfxError, LIB_PATH, lib
 from .brainvision import (ChannelInfo, EEGMarker, Header, plan_markers, read_header,
                           read_markers, read_raw, recording_frames)
-from .classification import DecisionTreeClassifier, dtree_predict, dtree_train
+from .classification import (DecisionTreeClassifier, RandomForestClassifier, dtree_predict,
+                             dtree_train, poisson_bag, rforest_predict, rforest_train)
 from .context import Context, device_count
 from .data_provider import OffLineDataProvider
 from .feature_extraction import IFeatureExtraction, WaveletTransform
 
 __all__ = [
     "Context", "ChannelInfo", "DecisionTreeClassifier", "EEGMarker", "EegfxError", "Header",
-    "IFeatureExtraction", "LIB_PATH", "OffLineDataProvider", "WaveletTransform", "device_count",
-    "dtree_predict", "dtree_train", "lib",
-    "plan_markers", "read_header", "read_markers", "read_raw", "recording_frames",
+    "IFeatureExtraction", "LIB_PATH", "OffLineDataProvider", "RandomForestClassifier",
+    "WaveletTransform", "device_count", "dtree_predict", "dtree_train", "lib",
+    "plan_markers", "poisson_bag", "read_header", "read_markers", "read_raw", "recording_frames",
+    "rforest_predict", "rforest_train",
 ]

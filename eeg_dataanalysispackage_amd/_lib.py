@@ -71,6 +71,7 @@ class OdpShard(Structure):
 
 ODP_MAX_SHARDS = 64
 GINI, ENTROPY = 0, 1
+SUBSET_AUTO, SUBSET_ALL, SUBSET_SQRT, SUBSET_LOG2, SUBSET_ONETHIRD = 0, 1, 2, 3, 4
 
 
 class TreeNode(Structure):
@@ -148,6 +149,12 @@ SIGNATURES = {
                                   c_int]),
     "eegfx_dtree_predict": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32,
                                     c_void_p, c_int]),
+    "eegfx_rforest_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
+                                    c_int64, c_void_p, c_int32, c_void_p, POINTER(c_int32), c_int]),
+    "eegfx_rforest_predict": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                      c_int32, c_void_p, c_int]),
+    "eegfx_poisson_bag": (c_int, [c_int64, c_int32, c_int32, c_int64, c_void_p]),
     "eegfx_svm_sgd_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                     c_double, c_double, c_double, c_double, c_void_p,
                                     POINTER(c_int32), c_int]),

@@ -10,7 +10,9 @@ including the reference's reading of the column-major confusion matrix (its "fal
 count actual-1 / predicted-0).  ``SVMClassifier`` is the same flow with MLlib 1.6.2
 ``SVMWithSGD`` (HingeGradient, ``eegfx_svm_sgd_train``) and ``SVMModel.predict`` (margin > 0).
 ``DecisionTreeClassifier`` (train_clf=dt) is the flow again with MLlib 1.6.2 ``DecisionTree``
-(``eegfx_dtree_train`` / ``eegfx_dtree_predict``).
+(``eegfx_dtree_train`` / ``eegfx_dtree_predict``), and
+``RandomForestClassifier`` (train_clf=rf) with MLlib 1.6.2 ``RandomForest``
+(``eegfx_rforest_train`` / ``eegfx_rforest_predict``).
 Model save/load (Spark model directories) is out of scope.
 """
 from __future__ import annotations
@@ -182,6 +184,96 @@ def dtree_predict(ctx: Context, X, nodes):
     ctx._call(mem, X, lib().eegfx_dtree_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
               int(nodes.shape[0]), ptr(out), mem)
     return out
+
+
+# RandomForestClassifier.java:101-136 without a complete config
+DEFAULT_NUM_TREES = 100
+DEFAULT_FEATURE_SUBSET = "auto"
+DEFAULT_FOREST_SEED = 12345
+FEATURE_SUBSETS = {"auto": _lib.SUBSET_AUTO, "all": _lib.SUBSET_ALL, "sqrt": _lib.SUBSET_SQRT,
+                   "log2": _lib.SUBSET_LOG2, "onethird": _lib.SUBSET_ONETHIRD}
+
+
+def rforest_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
+                  max_depth: int = DEFAULT_MAX_DEPTH, max_bins: int = DEFAULT_MAX_BINS,
+                  min_instances_per_node: int = DEFAULT_MIN_INSTANCES_PER_NODE,
+                  num_trees: int = DEFAULT_NUM_TREES, feature_subset: str = DEFAULT_FEATURE_SUBSET,
+                  seed: int = DEFAULT_FOREST_SEED, num_partitions: Optional[int] = None,
+                  split_seed: int = 0):
+    """MLlib 1.6.2 RandomForest (two classes, continuous features) on the device
+    (eegfx_rforest_train); returns (nodes, tree_offsets): the trees' nodes one tree after another,
+    as dtree_train returns one tree (children relative to the tree's first node), and tree t's
+    range tree_offsets[t]:tree_offsets[t + 1].  feature_subset: "auto", "all", "sqrt", "log2" or
+    "onethird".  seed seeds the bagging weights and the feature subsets (the reference: 12345),
+    num_partitions the slices of the training RDD the bagging samplers belong to (None: the
+    processors available to the process, as for sgd_train); the other arguments are dtree_train's.
+    num_trees = 1 with "auto" or "all" is dtree_train's tree."""
+    kinds = {"gini": _lib.GINI, "entropy": _lib.ENTROPY}
+    if impurity not in kinds:
+        raise ValueError(f"impurity must be one of {sorted(kinds)}, got {impurity!r}")
+    if feature_subset not in FEATURE_SUBSETS:
+        raise ValueError(f"feature_subset must be one of {sorted(FEATURE_SUBSETS)}, "
+                         f"got {feature_subset!r}")
+    if _is_device(X) != _is_device(y):
+        raise ValueError("X and y must both be host or both be device arrays")
+    X = _contig(X, np.float64)
+    y = _contig(y, np.float64)
+    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
+        raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
+    n, d = int(X.shape[0]), int(X.shape[1])
+    trees = max(int(num_trees), 1)
+    depth = min(max(int(max_depth), 0), 30)
+    # a first guess; the call reports the count needed when the forest is larger
+    capacity = max(1, trees * min(2 ** (depth + 1) - 1, 2 * n - 1, 1023))
+    offsets = np.zeros(trees + 1, dtype=np.int32)
+    count = c_int32()
+    mem = _mem(X, y)
+    while True:
+        nodes = np.zeros(capacity, dtype=TREE_NODE)
+        count.value = 0
+        try:
+            ctx._call(mem, X, lib().eegfx_rforest_train, ctx.handle, ptr(X), ptr(y), n, d,
+                      kinds[impurity], int(max_depth), int(max_bins), int(min_instances_per_node),
+                      int(num_trees), FEATURE_SUBSETS[feature_subset], int(seed),
+                      0 if num_partitions is None else int(num_partitions), int(split_seed),
+                      ptr(nodes), capacity, ptr(offsets), byref(count), mem)
+        except EegfxError:
+            if count.value <= capacity:
+                raise
+            capacity = count.value
+            continue
+        return nodes[:count.value].copy(), offsets
+
+
+def rforest_predict(ctx: Context, X, nodes, tree_offsets):
+    """RandomForestModel.predict on the device (eegfx_rforest_predict): 1.0 where more trees vote 1
+    than 0 for the row of X (host numpy or device torch), 0.0 otherwise (a tie included)."""
+    nodes = np.ascontiguousarray(nodes, dtype=TREE_NODE)
+    offsets = np.ascontiguousarray(tree_offsets, dtype=np.int32)
+    if offsets.ndim != 1 or offsets.shape[0] < 2 or int(offsets[-1]) != int(nodes.shape[0]):
+        raise ValueError("tree_offsets must hold one offset per tree and end at len(nodes)")
+    X = _contig(X, np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if _is_device(X):
+        import torch
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    else:
+        out = np.empty(n, dtype=np.float64)
+    mem = _mem(X, out)
+    ctx._call(mem, X, lib().eegfx_rforest_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
+              ptr(offsets), int(offsets.shape[0]) - 1, ptr(out), mem)
+    return out
+
+
+def poisson_bag(n: int, num_trees: int, num_partitions: int, seed: int) -> np.ndarray:
+    """The bagging weights of rforest_train (eegfx_poisson_bag, host only): uint8
+    [num_trees][n], Poisson(1) draws of one sampler per slice of the rows."""
+    from ._lib import check
+    w = np.zeros((max(int(num_trees), 0), max(int(n), 0)), dtype=np.uint8)
+    check(lib().eegfx_poisson_bag(int(n), int(num_trees), int(num_partitions), int(seed), ptr(w)))
+    return w
 
 
 class ClassificationStatistics:
@@ -369,6 +461,46 @@ class DecisionTreeClassifier(LogisticRegressionClassifier):
         return reference_statistics(pred, targets)
 
 
+class RandomForestClassifier(DecisionTreeClassifier):
+    """IClassifier for train_clf=rf (RandomForestClassifier.java), GPU-resident: the flow of
+    DecisionTreeClassifier with MLlib's RandomForest and RandomForestModel.predict."""
+
+    CONFIG_KEYS = ("config_max_bins", "config_impurity", "config_max_depth",
+                   "config_min_instances_per_node", "config_feature_subset", "config_num_trees")
+
+    def __init__(self, context: Optional[Context] = None):
+        super().__init__(context)
+        self.tree_offsets: Optional[np.ndarray] = None
+
+    def train(self, epochs, targets: Sequence[float], fe) -> None:
+        """:101-136 -- Strategy.defaultStrategy("Classification"), 100 trees, "auto", seed 12345;
+        with all six config keys set, their values instead ("gini" is Gini, any other string
+        Entropy; a feature subset that is no strategy's name is Spark's failed require)."""
+        self.fe = fe
+        X = self._features(epochs)
+        y = np.asarray(targets, dtype=np.float64)
+        c = self.config
+        kw = {}
+        if all(k in c for k in self.CONFIG_KEYS):
+            if c["config_feature_subset"] not in FEATURE_SUBSETS:
+                raise ValueError("requirement failed: RandomForest given invalid "
+                                 f"featureSubsetStrategy: {c['config_feature_subset']}")
+            kw = dict(impurity="gini" if c["config_impurity"] == "gini" else "entropy",
+                      max_depth=int(c["config_max_depth"]), max_bins=int(c["config_max_bins"]),
+                      min_instances_per_node=int(c["config_min_instances_per_node"]),
+                      num_trees=int(c["config_num_trees"]),
+                      feature_subset=c["config_feature_subset"])
+        self.nodes, self.tree_offsets = rforest_train(
+            self.context, X, y, num_partitions=self.num_partitions, split_seed=self.split_seed,
+            **kw)
+
+    def predict(self, features) -> np.ndarray:
+        if self.nodes is None:
+            raise RuntimeError("The classifier has not been trained")  # IllegalStateException
+        return rforest_predict(self.context, features, self.nodes, self.tree_offsets)
+
+
 __all__ = ["ClassificationStatistics", "DecisionTreeClassifier", "LogisticRegressionClassifier",
-           "SVMClassifier", "dtree_predict", "dtree_train", "predict", "reference_statistics",
+           "RandomForestClassifier", "SVMClassifier", "dtree_predict", "dtree_train",
+           "poisson_bag", "predict", "reference_statistics", "rforest_predict", "rforest_train",
            "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]

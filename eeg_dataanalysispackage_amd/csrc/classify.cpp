@@ -17,7 +17,7 @@
 // (Spark local[*]'s defaultParallelism, SparkInitializer.java:44): the affinity mask, capped by a
 // cgroup CPU quota (cgroup v2 cpu.max or v1 cfs_quota_us / cfs_period_us), at least 1.
 // std::thread::hardware_concurrency() counts every online CPU of the machine instead.
-static int available_processors() {
+int eegfx::available_processors() {
   int n = 0;
   cpu_set_t set;
   if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);

@@ -178,6 +178,9 @@ struct eegfx_ctx {
   // the decision tree (eegfx_dtree_*): threshold table, bins, slot + label per row, one group's
   // histograms (and the gathered split sample), a level's decisions / the nodes of a prediction
   DevBuf dt_tab, dt_bins, dt_rows, dt_hist, dt_dec;
+  // the random forest (eegfx_rforest_*) on top of them: weight per tree and row, slot per tree and
+  // row, a group's feature subsets and launch tree lists / the tree offsets of a prediction
+  DevBuf rf_weight, rf_slot, rf_tab;
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
   PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
                                          // a sharded provider's worker: the file spans it reads
@@ -206,12 +209,14 @@ struct eegfx_ctx {
   }
   void bind_buffers() {
     for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec})
+                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec,
+                      &rf_weight, &rf_slot, &rf_tab})
       b->sp = &stream;
   }
   void release_buffers() {
     for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec})
+                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec,
+                      &rf_weight, &rf_slot, &rf_tab})
       b->release();
     pin_in.release();
     pin_out.release();
@@ -330,6 +335,24 @@ struct eegfx_ctx {
 namespace eegfx {
 
 void check_mem(int mem);
+// The processors this process may run on (classify.cpp): Spark local[*]'s defaultParallelism.
+int available_processors();
+// dtree_driver.cpp: the binned rows of a tree or forest call.  Host: the threshold table `tab`
+// (int32 flags[4], nthr[d], double thr[d][T]); device: the same table, bins uint8 [n][d], slot
+// int32 [n] = 0, label uint8 [n], and the scratch allocation for the histograms.
+struct DtBinned {
+  int B = 0, T = 0;  // numBins, numSplits
+  std::vector<uint8_t> tab;
+  int32_t* nthr = nullptr;
+  double* thr = nullptr;
+  uint8_t* dtab = nullptr;
+  uint8_t* bins = nullptr;
+  int32_t* slot = nullptr;
+  uint8_t* label = nullptr;
+  void* scratch = nullptr;
+};
+void dt_bin_rows(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                 int32_t max_bins, int64_t split_seed, int mem, size_t hist_bytes, DtBinned* out);
 // The raw entries' argument ladder up to the null-buffer check (api.cpp check_raw_args goes on
 // from it).  `mem`: EEGFX_MEM_HOST from an entry without a mem flag.
 void check_raw_head(const eegfx_ctx* ctx, int mem, const void* raw, int fmt, int64_t n_frames,

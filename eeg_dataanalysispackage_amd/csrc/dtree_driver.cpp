@@ -14,6 +14,107 @@
 // counters; a level with more active nodes than fit is histogrammed group by group).
 static constexpr size_t kDtHistBudget = (size_t)16 << 20;
 
+// The front half of a tree or a forest call (DESIGN.md section 10.1 "Bins"): the threshold sample
+// to the host, the thresholds of every feature (one sort per feature, on threads), the table to
+// the device and the rows binned there.  hist_bytes: what the caller's histograms need of the
+// scratch allocation that also holds the gathered sample.
+void eegfx::dt_bin_rows(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                        int32_t max_bins, int64_t split_seed, int mem, size_t hist_bytes,
+                        DtBinned* out) {
+  DtBinned& b = *out;
+  const hipStream_t st = ctx->stream;
+  const int B = b.B = (int)std::min<int64_t>(max_bins, n), T = b.T = B - 1;  // numBins, numSplits
+  // ---- the sampled rows, on the host
+  const int64_t required = dtree::required_samples(max_bins);
+  std::vector<int64_t> rows;  // empty: every row
+  if (n > required) {
+    std::vector<uint32_t> mask((size_t)((n + 31) / 32));
+    spark::sample_mask(n, (double)required / (double)n, 1, split_seed, mask.data());
+    for (int64_t r = 0; r < n; ++r)
+      if ((mask[r >> 5] >> (r & 31)) & 1u) rows.push_back(r);
+  }
+  const int64_t m = rows.empty() && n <= required ? n : (int64_t)rows.size();
+  if (m < 1) fail(EEGFX_EINVAL, "the split sample is empty");
+
+  const double* dX = X;
+  const double* dy = y;
+  if (mem == EEGFX_MEM_HOST) {
+    double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
+    double* by = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
+    HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(by, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+    dX = bx;
+    dy = by;
+  }
+  // one allocation for the sample (device X only) and the histograms of a group after it
+  const size_t sample_bytes = mem == EEGFX_MEM_DEVICE ? sizeof(double) * (size_t)(m * d) : 0;
+  const size_t idx_bytes = sizeof(int64_t) * rows.size();
+  b.scratch = ctx->dt_hist.get(std::max(sample_bytes + idx_bytes, hist_bytes));
+  std::vector<double> sample;  // [m][d]
+  const double* S = X;
+  if (mem == EEGFX_MEM_DEVICE) {
+    sample.resize((size_t)(m * d));
+    if (rows.empty()) {
+      HIP_CHECK(hipMemcpyAsync(sample.data(), dX, sample_bytes, hipMemcpyDeviceToHost, st));
+    } else {
+      int64_t* didx = (int64_t*)((char*)b.scratch + sample_bytes);
+      HIP_CHECK(hipMemcpyAsync(didx, rows.data(), idx_bytes, hipMemcpyHostToDevice, st));
+      HIP_CHECK(launch_dt_gather(st, dX, d, didx, m, (double*)b.scratch));
+      HIP_CHECK(hipMemcpyAsync(sample.data(), b.scratch, sample_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    S = sample.data();
+  }
+
+  // ---- thresholds: int32 flags[4], int32 nthr[d] (padded to 8 bytes), double thr[d][T]
+  const size_t thr_off = 16 + (((size_t)d * 4 + 7) & ~(size_t)7);
+  b.tab.assign(thr_off + sizeof(double) * (size_t)d * T, 0);
+  int32_t* nthr = b.nthr = (int32_t*)(b.tab.data() + 16);
+  double* thr = b.thr = (double*)(b.tab.data() + thr_off);
+  {
+    const bool packed = mem == EEGFX_MEM_DEVICE || rows.empty();  // S holds the sample itself
+    // Spark 1.6 finds no bin for a non-finite value and throws
+    for (int64_t i = 0; i < m; ++i) {
+      const double* row = S + (packed ? i : rows[i]) * d;
+      for (int f = 0; f < d; ++f)
+        if (!std::isfinite(row[f])) fail(EEGFX_EINVAL, "a training feature is not finite");
+    }
+    // one sort per feature, threads over the features (the sorts are
+    // most of a call's time on one thread)
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const int W = (int)std::min({(unsigned)d, 8u, hw});
+    std::vector<char> failed((size_t)W, 0);  // no exception leaves a thread
+    {
+      Joiner pool;
+      for (int w = 0; w < W; ++w)
+        pool.th.emplace_back([&, w] {
+          try {
+            std::vector<double> col((size_t)m), t;
+            for (int f = w; f < d; f += W) {
+              for (int64_t i = 0; i < m; ++i) col[i] = S[(packed ? i : rows[i]) * d + f];
+              dtree::find_thresholds(col, T, &t);
+              // at most T by find_thresholds' argument; never past the feature's table row
+              nthr[f] = (int32_t)std::min<size_t>(t.size(), (size_t)T);
+              std::copy(t.begin(), t.begin() + nthr[f], thr + (size_t)f * T);
+            }
+          } catch (...) {
+            failed[w] = 1;
+          }
+        });
+    }
+    for (char c : failed)
+      if (c) fail(EEGFX_ENOMEM, "out of host memory in the threshold search");
+  }
+  uint8_t* dtab = b.dtab = (uint8_t*)ctx->dt_tab.get(b.tab.size());
+  HIP_CHECK(hipMemcpyAsync(dtab, b.tab.data(), b.tab.size(), hipMemcpyHostToDevice, st));
+  uint8_t* bins = b.bins = (uint8_t*)ctx->dt_bins.get((size_t)(n * d));
+  // int32 slot[n], then uint8 label[n]
+  int32_t* slot = b.slot = (int32_t*)ctx->dt_rows.get(5 * (size_t)n);
+  uint8_t* label = b.label = (uint8_t*)(slot + n);
+  HIP_CHECK(launch_dt_bin(st, dX, dy, n, d, T, (const int32_t*)(dtab + 16),
+                          (const double*)(dtab + thr_off), (int32_t*)dtab, bins, label, slot));
+}
+
 extern "C" {
 
 int eegfx_dtree_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
@@ -47,95 +148,16 @@ int eegfx_dtree_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t 
     if (node_counters <= (size_t)kDtLdsCounters)
       G = std::min(G, (int)(kDtLdsCounters / node_counters));
 
-    // ---- the sampled rows, on the host
-    const int64_t required = dtree::required_samples(max_bins);
-    std::vector<int64_t> rows;  // empty: every row
-    if (n > required) {
-      std::vector<uint32_t> mask((size_t)((n + 31) / 32));
-      spark::sample_mask(n, (double)required / (double)n, 1, split_seed, mask.data());
-      for (int64_t r = 0; r < n; ++r)
-        if ((mask[r >> 5] >> (r & 31)) & 1u) rows.push_back(r);
-    }
-    const int64_t m = rows.empty() && n <= required ? n : (int64_t)rows.size();
-    if (m < 1) fail(EEGFX_EINVAL, "the split sample is empty");
-
-    const double* dX = X;
-    const double* dy = y;
-    if (mem == EEGFX_MEM_HOST) {
-      double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
-      double* by = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
-      HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(by, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-      dX = bx;
-      dy = by;
-    }
-    // one allocation for the sample (device X only) and the histograms of a group after it
-    const size_t sample_bytes = mem == EEGFX_MEM_DEVICE ? sizeof(double) * (size_t)(m * d) : 0;
-    const size_t idx_bytes = sizeof(int64_t) * rows.size();
-    void* scratch = ctx->dt_hist.get(std::max(sample_bytes + idx_bytes, (size_t)G * node_bytes));
-    std::vector<double> sample;  // [m][d]
-    const double* S = X;
-    if (mem == EEGFX_MEM_DEVICE) {
-      sample.resize((size_t)(m * d));
-      if (rows.empty()) {
-        HIP_CHECK(hipMemcpyAsync(sample.data(), dX, sample_bytes, hipMemcpyDeviceToHost, st));
-      } else {
-        int64_t* didx = (int64_t*)((char*)scratch + sample_bytes);
-        HIP_CHECK(hipMemcpyAsync(didx, rows.data(), idx_bytes, hipMemcpyHostToDevice, st));
-        HIP_CHECK(launch_dt_gather(st, dX, d, didx, m, (double*)scratch));
-        HIP_CHECK(hipMemcpyAsync(sample.data(), scratch, sample_bytes, hipMemcpyDeviceToHost, st));
-      }
-      HIP_CHECK(hipStreamSynchronize(st));
-      S = sample.data();
-    }
-
-    // ---- thresholds: int32 flags[4], int32 nthr[d] (padded to 8 bytes), double thr[d][T]
-    const size_t thr_off = 16 + (((size_t)d * 4 + 7) & ~(size_t)7);
-    std::vector<uint8_t> tab(thr_off + sizeof(double) * (size_t)d * T, 0);
-    int32_t* nthr = (int32_t*)(tab.data() + 16);
-    double* thr = (double*)(tab.data() + thr_off);
-    {
-      const bool packed = mem == EEGFX_MEM_DEVICE || rows.empty();  // S holds the sample itself
-      // Spark 1.6 finds no bin for a non-finite value and throws
-      for (int64_t i = 0; i < m; ++i) {
-        const double* row = S + (packed ? i : rows[i]) * d;
-        for (int f = 0; f < d; ++f)
-          if (!std::isfinite(row[f])) fail(EEGFX_EINVAL, "a training feature is not finite");
-      }
-      // one sort per feature, threads over the features (the sorts are
-      // most of a call's time on one thread)
-      const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-      const int W = (int)std::min({(unsigned)d, 8u, hw});
-      std::vector<char> failed((size_t)W, 0);  // no exception leaves a thread
-      {
-        Joiner pool;
-        for (int w = 0; w < W; ++w)
-          pool.th.emplace_back([&, w] {
-            try {
-              std::vector<double> col((size_t)m), t;
-              for (int f = w; f < d; f += W) {
-                for (int64_t i = 0; i < m; ++i) col[i] = S[(packed ? i : rows[i]) * d + f];
-                dtree::find_thresholds(col, T, &t);
-                // at most T by find_thresholds' argument; never past the feature's table row
-                nthr[f] = (int32_t)std::min<size_t>(t.size(), (size_t)T);
-                std::copy(t.begin(), t.begin() + nthr[f], thr + (size_t)f * T);
-              }
-            } catch (...) {
-              failed[w] = 1;
-            }
-          });
-      }
-      for (char c : failed)
-        if (c) fail(EEGFX_ENOMEM, "out of host memory in the threshold search");
-    }
-    uint8_t* dtab = (uint8_t*)ctx->dt_tab.get(tab.size());
-    HIP_CHECK(hipMemcpyAsync(dtab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
-    uint8_t* bins = (uint8_t*)ctx->dt_bins.get((size_t)(n * d));
-    // int32 slot[n], then uint8 label[n]
-    int32_t* slot = (int32_t*)ctx->dt_rows.get(5 * (size_t)n);
-    uint8_t* label = (uint8_t*)(slot + n);
-    HIP_CHECK(launch_dt_bin(st, dX, dy, n, d, T, (const int32_t*)(dtab + 16),
-                            (const double*)(dtab + thr_off), (int32_t*)dtab, bins, label, slot));
+    DtBinned binned;
+    dt_bin_rows(ctx, X, y, n, d, max_bins, split_seed, mem, (size_t)G * node_bytes, &binned);
+    const int32_t* nthr = binned.nthr;
+    const double* thr = binned.thr;
+    std::vector<uint8_t>& tab = binned.tab;
+    uint8_t* const dtab = binned.dtab;
+    uint8_t* const bins = binned.bins;
+    uint8_t* const label = binned.label;
+    int32_t* const slot = binned.slot;
+    void* const scratch = binned.scratch;
 
     // ---- the tree, level by level
     std::vector<eegfx_tree_node> out;

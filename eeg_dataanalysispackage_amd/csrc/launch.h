@@ -213,4 +213,26 @@ hipError_t launch_dt_gather(hipStream_t st, const double* X, int d, const int64_
 hipError_t launch_dt_predict(hipStream_t st, const double* X, int64_t n, int d,
                              const DtNode* nodes, int n_nodes, double* out);
 
+// rforest.hip: the passes of the random forest over every tree's rows (eegfx_rforest_*; the host
+// half is rforest_host.h).  weight uint8 [tree][row], slot int32 [tree][row]: the queue ticket of
+// the row's node in that tree, -1: a leaf or weight 0.
+hipError_t launch_rf_init(hipStream_t st, const uint8_t* weight, int64_t n, int num_trees,
+                          int32_t* slot);
+// hist uint32 [g][k][B][2] (zeroed by the caller) += the weights of the rows whose slot lies in
+// [s0, s0 + g), over trees[nt] (the distinct trees of those nodes); sub int32 [g][k]: the features
+// of each node, nullptr: features 0..k-1 (k == d).  Privatised in LDS when g * k * B * 2 <=
+// kDtLdsCounters, else global atomics.
+hipError_t launch_rf_hist(hipStream_t st, const uint8_t* bins, const uint8_t* label,
+                          const uint8_t* weight, const int32_t* slot, int64_t n, int d, int B,
+                          int k, int s0, int g, const int32_t* trees, int nt, const int32_t* sub,
+                          uint32_t* hist);
+// dec[g]: the outcome of tickets [s0, s0 + g), left / right = the children's tickets
+hipError_t launch_rf_route(hipStream_t st, const uint8_t* bins, int64_t n, int d,
+                           const int32_t* trees, int nt, int s0, int g, const DtDecision* dec,
+                           int32_t* slot);
+// nodes: the trees concatenated, children relative to their tree's first node; offsets[trees + 1]
+hipError_t launch_rf_predict(hipStream_t st, const double* X, int64_t n, int d,
+                             const DtNode* nodes, const int32_t* offsets, int num_trees,
+                             double* out);
+
 }  // namespace eegfx

@@ -27,8 +27,8 @@
  * that synchronises it, which also clears it.  The calls that synchronise are
  * eegfx_ctx_synchronize, eegfx_ctx_guard_stats / _detail, every EEGFX_MEM_HOST compute call,
  * eegfx_read_raw with EEGFX_MEM_DEVICE, eegfx_logreg_sgd_train / eegfx_svm_sgd_train /
- * eegfx_dtree_train, and eegfx_logreg_predict / eegfx_svm_predict / eegfx_dtree_predict with
- * EEGFX_MEM_DEVICE.  When such a call returns
+ * eegfx_dtree_train / eegfx_rforest_train, and eegfx_logreg_predict / eegfx_svm_predict /
+ * eegfx_dtree_predict / eegfx_rforest_predict with EEGFX_MEM_DEVICE.  When such a call returns
  * EEGFX_ERANGE for an earlier call's position, its own work has completed and its outputs are
  * valid; the rows of the epochs with the refused positions are unspecified.  Results of
  * EEGFX_MEM_DEVICE calls are unspecified until a synchronising call has returned EEGFX_OK.  Host
@@ -404,6 +404,44 @@ int eegfx_dtree_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t 
 int eegfx_dtree_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
                         const eegfx_tree_node* nodes /* host */, int32_t n_nodes, double* out,
                         int mem);
+
+/* ---- train_clf=rf: the random forest (RandomForestClassifier.java:101-136) --------------------
+ * MLlib 1.6.2 RandomForest over continuous features and two classes, as DESIGN.md section 10.2
+ * states it: the decision tree's thresholds and bins (one table for all trees); every tree's row
+ * weights from commons-math's PoissonDistribution(1.0) on a Well19937c, one sampler per
+ * ParallelCollectionRDD slice seeded with seed + slice + 1 (num_trees == 1: every weight 1);
+ * feature_subset features per node (AUTO: ALL for one tree, else SQRT), drawn per node by reservoir
+ * sampling seeded from java.util.Random(seed); nodes split in queue order, in groups of at most
+ * 256 MB of aggregates; prediction is the majority of the trees' votes, 0.0 on a tie.  The
+ * weights and the weighted histograms are integers and the gains the decision tree's fp64, so
+ * the forest is defined bit for bit.  eegfx_rforest_train writes the trees one after another into
+ * the host array `nodes` (each ascending by `id`, `left` / `right` relative to the tree's first
+ * node) and tree t's range into tree_offsets[t], tree_offsets[t + 1]; when `capacity` is too
+ * small it returns EEGFX_EINVAL with the count needed in *n_nodes.  num_trees = 1 with AUTO or ALL
+ * is eegfx_dtree_train's tree.  num_partitions 0: the processors available to the process, as
+ * eegfx_logreg_sgd_train takes them.  Limits: eegfx_dtree_train's, num_trees >= 1,
+ * num_partitions >= 0; a Poisson draw above 255 or a tree whose weights sum above 2^32 - 1 is
+ * EEGFX_ENOTSUP.  eegfx_rforest_predict refuses (EEGFX_EINVAL) offsets that do not ascend from 0
+ * and a tree that eegfx_dtree_predict would refuse.  eegfx_poisson_bag (pure host function) writes
+ * the weights uint8 [num_trees][n] the training draws. */
+#define EEGFX_SUBSET_AUTO 0
+#define EEGFX_SUBSET_ALL 1
+#define EEGFX_SUBSET_SQRT 2
+#define EEGFX_SUBSET_LOG2 3
+#define EEGFX_SUBSET_ONETHIRD 4
+int eegfx_rforest_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                        int32_t impurity, int32_t max_depth, int32_t max_bins,
+                        int32_t min_instances_per_node, int32_t num_trees, int32_t feature_subset,
+                        int64_t seed /* the reference: 12345 */, int32_t num_partitions,
+                        int64_t split_seed, eegfx_tree_node* nodes /* host */, int32_t capacity,
+                        int32_t* tree_offsets /* host, [num_trees + 1] */, int32_t* n_nodes,
+                        int mem);
+int eegfx_rforest_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
+                          const eegfx_tree_node* nodes /* host */,
+                          const int32_t* tree_offsets /* host */, int32_t num_trees, double* out,
+                          int mem);
+int eegfx_poisson_bag(int64_t n, int32_t num_trees, int32_t num_partitions, int64_t seed,
+                      uint8_t* weights);
 
 /* eegfx_svm_* (MLlib SVMWithSGD on the same device loop) is declared in eegfx_ext.h: SURVEY.md
  * section 2 marks the SVM classifier out of the hot-path scope, so it is not part of this contract. */
