@@ -59,15 +59,20 @@ def _train(entry, ctx: Context, X, y, num_iterations, step_size, reg_param, mini
     return w, it.value
 
 
+def _predict_out(X):
+    """One float64 per row of X, on X's side (a torch tensor on its device, else numpy)."""
+    n = int(X.shape[0])
+    if _is_device(X):
+        import torch
+        return torch.empty(n, dtype=torch.float64, device=X.device)
+    return np.empty(n, dtype=np.float64)
+
+
 def _predict(entry, ctx: Context, X, weights, intercept, threshold):
     w = np.ascontiguousarray(weights, dtype=np.float64)
     X = _contig(X, np.float64)
     n, d = int(X.shape[0]), int(X.shape[1])
-    if _is_device(X):
-        import torch
-        out = torch.empty(n, dtype=torch.float64, device=X.device)
-    else:
-        out = np.empty(n, dtype=np.float64)
+    out = _predict_out(X)
     t = math.nan if threshold is None else float(threshold)
     mem = _mem(X, out)
     ctx._call(mem, X, getattr(lib(), entry), ctx.handle, ptr(X), n, d, ptr(w), float(intercept),
@@ -135,6 +140,21 @@ DEFAULT_MIN_INSTANCES_PER_NODE = 1
 TREE_NODE = np.dtype(_lib.TreeNode)
 
 
+def _tree_inputs(X, y, impurity):
+    """The checks dtree_train and rforest_train share: (X, y) contiguous float64 [n][d] and [n] on
+    one side, and the impurity's code."""
+    kinds = {"gini": _lib.GINI, "entropy": _lib.ENTROPY}
+    if impurity not in kinds:
+        raise ValueError(f"impurity must be one of {sorted(kinds)}, got {impurity!r}")
+    if _is_device(X) != _is_device(y):
+        raise ValueError("X and y must both be host or both be device arrays")
+    X = _contig(X, np.float64)
+    y = _contig(y, np.float64)
+    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
+        raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
+    return X, y, kinds[impurity]
+
+
 def dtree_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
                 max_depth: int = DEFAULT_MAX_DEPTH, max_bins: int = DEFAULT_MAX_BINS,
                 min_instances_per_node: int = DEFAULT_MIN_INSTANCES_PER_NODE,
@@ -145,15 +165,7 @@ def dtree_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
     X (n x d float64, host numpy or device torch) and y (n labels 0/1) may live on either side.
     impurity: "gini" or "entropy".  split_seed seeds the Bernoulli sample of the rows the
     thresholds come from when n > max(max_bins^2, 10000) (Spark draws it fresh on every run)."""
-    kinds = {"gini": _lib.GINI, "entropy": _lib.ENTROPY}
-    if impurity not in kinds:
-        raise ValueError(f"impurity must be one of {sorted(kinds)}, got {impurity!r}")
-    if _is_device(X) != _is_device(y):
-        raise ValueError("X and y must both be host or both be device arrays")
-    X = _contig(X, np.float64)
-    y = _contig(y, np.float64)
-    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
-        raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
+    X, y, kind = _tree_inputs(X, y, impurity)
     n, d = int(X.shape[0]), int(X.shape[1])
     # every leaf holds a row and no node lies below max_depth
     depth = min(max(int(max_depth), 0), 30)
@@ -161,7 +173,7 @@ def dtree_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
     nodes = np.zeros(capacity, dtype=TREE_NODE)
     count = c_int32()
     mem = _mem(X, y)
-    ctx._call(mem, X, lib().eegfx_dtree_train, ctx.handle, ptr(X), ptr(y), n, d, kinds[impurity],
+    ctx._call(mem, X, lib().eegfx_dtree_train, ctx.handle, ptr(X), ptr(y), n, d, kind,
               int(max_depth), int(max_bins), int(min_instances_per_node), int(split_seed),
               ptr(nodes), capacity, byref(count), mem)
     return nodes[:count.value].copy()
@@ -175,11 +187,7 @@ def dtree_predict(ctx: Context, X, nodes):
     if X.ndim != 2:
         raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
     n, d = int(X.shape[0]), int(X.shape[1])
-    if _is_device(X):
-        import torch
-        out = torch.empty(n, dtype=torch.float64, device=X.device)
-    else:
-        out = np.empty(n, dtype=np.float64)
+    out = _predict_out(X)
     mem = _mem(X, out)
     ctx._call(mem, X, lib().eegfx_dtree_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
               int(nodes.shape[0]), ptr(out), mem)
@@ -208,18 +216,10 @@ def rforest_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
     num_partitions the slices of the training RDD the bagging samplers belong to (None: the
     processors available to the process, as for sgd_train); the other arguments are dtree_train's.
     num_trees = 1 with "auto" or "all" is dtree_train's tree."""
-    kinds = {"gini": _lib.GINI, "entropy": _lib.ENTROPY}
-    if impurity not in kinds:
-        raise ValueError(f"impurity must be one of {sorted(kinds)}, got {impurity!r}")
+    X, y, kind = _tree_inputs(X, y, impurity)
     if feature_subset not in FEATURE_SUBSETS:
         raise ValueError(f"feature_subset must be one of {sorted(FEATURE_SUBSETS)}, "
                          f"got {feature_subset!r}")
-    if _is_device(X) != _is_device(y):
-        raise ValueError("X and y must both be host or both be device arrays")
-    X = _contig(X, np.float64)
-    y = _contig(y, np.float64)
-    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
-        raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
     n, d = int(X.shape[0]), int(X.shape[1])
     trees = max(int(num_trees), 1)
     depth = min(max(int(max_depth), 0), 30)
@@ -233,7 +233,7 @@ def rforest_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
         count.value = 0
         try:
             ctx._call(mem, X, lib().eegfx_rforest_train, ctx.handle, ptr(X), ptr(y), n, d,
-                      kinds[impurity], int(max_depth), int(max_bins), int(min_instances_per_node),
+                      kind, int(max_depth), int(max_bins), int(min_instances_per_node),
                       int(num_trees), FEATURE_SUBSETS[feature_subset], int(seed),
                       0 if num_partitions is None else int(num_partitions), int(split_seed),
                       ptr(nodes), capacity, ptr(offsets), byref(count), mem)
@@ -256,11 +256,7 @@ def rforest_predict(ctx: Context, X, nodes, tree_offsets):
     if X.ndim != 2:
         raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
     n, d = int(X.shape[0]), int(X.shape[1])
-    if _is_device(X):
-        import torch
-        out = torch.empty(n, dtype=torch.float64, device=X.device)
-    else:
-        out = np.empty(n, dtype=np.float64)
+    out = _predict_out(X)
     mem = _mem(X, out)
     ctx._call(mem, X, lib().eegfx_rforest_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
               ptr(offsets), int(offsets.shape[0]) - 1, ptr(out), mem)
@@ -419,9 +415,20 @@ class SVMClassifier(LogisticRegressionClassifier):
         return svm_predict(self.context, features, self.weights)
 
 
+def _tree_config(c: Dict[str, str]) -> dict:
+    """The four config_* keys both tree classifiers read, as arguments of dtree_train and
+    rforest_train ("gini" is Gini, any other string Entropy)."""
+    return dict(impurity="gini" if c["config_impurity"] == "gini" else "entropy",
+                max_depth=int(c["config_max_depth"]), max_bins=int(c["config_max_bins"]),
+                min_instances_per_node=int(c["config_min_instances_per_node"]))
+
+
 class DecisionTreeClassifier(LogisticRegressionClassifier):
     """IClassifier for train_clf=dt (DecisionTreeClassifier.java), GPU-resident: the flow of
     LogisticRegressionClassifier with MLlib's DecisionTree and DecisionTreeModel.predict."""
+
+    CONFIG_KEYS = ("config_max_bins", "config_impurity", "config_max_depth",
+                   "config_min_instances_per_node")
 
     def __init__(self, context: Optional[Context] = None):
         super().__init__(context)
@@ -438,16 +445,8 @@ class DecisionTreeClassifier(LogisticRegressionClassifier):
         X = self._features(epochs)
         y = np.asarray(targets, dtype=np.float64)
         c = self.config
-        if all(k in c for k in ("config_max_bins", "config_impurity", "config_max_depth",
-                                "config_min_instances_per_node")):
-            self.nodes = dtree_train(
-                self.context, X, y,
-                impurity="gini" if c["config_impurity"] == "gini" else "entropy",
-                max_depth=int(c["config_max_depth"]), max_bins=int(c["config_max_bins"]),
-                min_instances_per_node=int(c["config_min_instances_per_node"]),
-                split_seed=self.split_seed)
-        else:
-            self.nodes = dtree_train(self.context, X, y, split_seed=self.split_seed)
+        kw = _tree_config(c) if all(k in c for k in self.CONFIG_KEYS) else {}
+        self.nodes = dtree_train(self.context, X, y, split_seed=self.split_seed, **kw)
 
     def predict(self, features) -> np.ndarray:
         if self.nodes is None:
@@ -465,8 +464,8 @@ class RandomForestClassifier(DecisionTreeClassifier):
     """IClassifier for train_clf=rf (RandomForestClassifier.java), GPU-resident: the flow of
     DecisionTreeClassifier with MLlib's RandomForest and RandomForestModel.predict."""
 
-    CONFIG_KEYS = ("config_max_bins", "config_impurity", "config_max_depth",
-                   "config_min_instances_per_node", "config_feature_subset", "config_num_trees")
+    CONFIG_KEYS = DecisionTreeClassifier.CONFIG_KEYS + ("config_feature_subset",
+                                                        "config_num_trees")
 
     def __init__(self, context: Optional[Context] = None):
         super().__init__(context)
@@ -485,10 +484,7 @@ class RandomForestClassifier(DecisionTreeClassifier):
             if c["config_feature_subset"] not in FEATURE_SUBSETS:
                 raise ValueError("requirement failed: RandomForest given invalid "
                                  f"featureSubsetStrategy: {c['config_feature_subset']}")
-            kw = dict(impurity="gini" if c["config_impurity"] == "gini" else "entropy",
-                      max_depth=int(c["config_max_depth"]), max_bins=int(c["config_max_bins"]),
-                      min_instances_per_node=int(c["config_min_instances_per_node"]),
-                      num_trees=int(c["config_num_trees"]),
+            kw = dict(_tree_config(c), num_trees=int(c["config_num_trees"]),
                       feature_subset=c["config_feature_subset"])
         self.nodes, self.tree_offsets = rforest_train(
             self.context, X, y, num_partitions=self.num_partitions, split_seed=self.split_seed,

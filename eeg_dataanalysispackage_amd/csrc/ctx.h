@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "eegfx_ext.h"
+#include "joiner.h"
 #include "launch.h"
 #include "mailbox.h"
 
@@ -132,16 +133,6 @@ ChanSel make_sel(const int32_t* cols, const float* res, int C, int ct);
 void check_positions(const int64_t* pos, int64_t n, int64_t n_frames);
 void check_fe_params(int C, int name, int epoch_size, int skip, int feature_size);
 bool wide_features(int feature_size);
-
-// Joins the threads it holds when it goes out of scope (an exception from emplace_back or from a
-// later call leaves no joinable std::thread behind, which would call std::terminate).
-struct Joiner {
-  std::vector<std::thread> th;
-  ~Joiner() {
-    for (auto& t : th)
-      if (t.joinable()) t.join();
-  }
-};
 
 }  // namespace eegfx
 
@@ -337,7 +328,7 @@ namespace eegfx {
 void check_mem(int mem);
 // The processors this process may run on (classify.cpp): Spark local[*]'s defaultParallelism.
 int available_processors();
-// dtree_driver.cpp: the binned rows of a tree or forest call.  Host: the threshold table `tab`
+// tree_driver.cpp: the binned rows of a tree or forest call.  Host: the threshold table `tab`
 // (int32 flags[4], nthr[d], double thr[d][T]); device: the same table, bins uint8 [n][d], slot
 // int32 [n] = 0, label uint8 [n], and the scratch allocation for the histograms.
 struct DtBinned {

@@ -1,23 +1,25 @@
 // dtree.hip -- the O(n d) passes of train_clf=dt on the GPU: MLlib 1.6.2
 // DecisionTree as Classification/DecisionTreeClassifier.java:99-127 runs it.  The host
-// (dtree_driver.cpp over dtree_host.h) finds the thresholds from the sampled rows and chooses
-// every split from integer histograms; these kernels do everything that touches all rows:
+// (tree_driver.cpp over dtree_host.h) finds the thresholds from the sampled rows and chooses
+// every split from integer histograms; these kernels do everything that touches all rows (the
+// rows are routed to their children by rforest.hip's rf_route_kernel, with one tree):
 //   dt_bin_kernel      X double[n][d] -> bins uint8[n][d] by binary search in the per-feature
 //                      threshold table (bin = thresholds below the value; bin k is (t[k-1], t[k]]),
 //                      labels -> uint8, every row's node slot = 0 (the root); flags a non-finite
 //                      feature and a label other than 0.0 / 1.0, as lr_validate_kernel does.
-//   dt_hist_kernel     one pass per level and group of active nodes: a row whose slot lies in the
-//                      group adds 1 to hist[slot][feature][bin][label].  A wave takes a row, its
-//                      lanes the features (lane k: k, k + 64, ...), so the lanes of one LDS atomic
-//                      hit distinct counters.  Privatised in 128 KB of LDS per workgroup and merged
-//                      with integer atomics (counts: no order enters the result); a group whose
-//                      histograms do not fit LDS adds to global memory directly.
-//   dt_route_kernel    slot -> the child's slot of the next level, or -1 when the child is a leaf.
+//   dt_hist_kernel     one pass per launch of g queued nodes (tickets g0 .. g0 + g - 1): a row
+//                      whose slot lies there adds 1 to hist[slot - g0][feature][bin][label].  A
+//                      wave takes a row, its lanes the features (lane k: k, k + 64, ...), so the
+//                      lanes of one LDS atomic hit distinct counters.  Privatised in 128 KB of LDS
+//                      per workgroup and merged with integer atomics (hist_lds.h; counts: no order
+//                      enters the result); a launch whose histograms do not fit LDS adds to global
+//                      memory directly.
 //   dt_predict_kernel  one row per lane walks the node array: left iff x[feature] <= threshold.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "hist_lds.h"
 #include "launch.h"
 
 namespace eegfx {
@@ -75,10 +77,7 @@ __global__ __launch_bounds__(kDtHistThreads) void dt_hist_kernel(
   __shared__ uint32_t h[LDS ? kDtLdsCounters : 1];
   const int node_counters = d * B * 2;
   const int used = LDS ? g * node_counters : 0;  // <= kDtLdsCounters (launch_dt_hist)
-  if (LDS) {
-    for (int i = threadIdx.x; i < used; i += blockDim.x) h[i] = 0;
-    __syncthreads();
-  }
+  if (LDS) lds_hist_zero(h, used);
   const int lane = threadIdx.x & 63;
   const int waves = (int)blockDim.x >> 6;
   constexpr int U = ONE ? kDtHistWide : kDtHistRows;
@@ -115,28 +114,7 @@ __global__ __launch_bounds__(kDtHistThreads) void dt_hist_kernel(
       }
     }
   }
-  if (LDS) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < used; i += blockDim.x) {
-      const uint32_t v = h[i];
-      if (v) atomicAdd(&hist[i], v);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void dt_route_kernel(const uint8_t* __restrict__ bins, int64_t n,
-                                                       int d, const DtDecision* __restrict__ dec,
-                                                       int32_t* __restrict__ slot) {
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n;
-       r += (int64_t)gridDim.x * blockDim.x) {
-    const int s = slot[r];
-    if (s < 0) continue;
-    const DtDecision dc = dec[s];
-    if (dc.feature < 0)
-      slot[r] = -1;
-    else
-      slot[r] = (int)bins[r * d + dc.feature] <= dc.split ? dc.left : dc.right;
-  }
+  if (LDS) lds_hist_merge(h, used, hist);
 }
 
 __global__ __launch_bounds__(256) void dt_gather_kernel(const double* __restrict__ X, int d,
@@ -165,15 +143,10 @@ __global__ __launch_bounds__(256) void dt_predict_kernel(const double* __restric
 
 }  // namespace dev
 
-static unsigned dt_grid(int64_t items, int per_block, int64_t cap) {
-  const int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 hipError_t launch_dt_bin(hipStream_t st, const double* X, const double* y, int64_t n, int d,
                          int T, const int32_t* nthr, const double* thr, int32_t* flags,
                          uint8_t* bins, uint8_t* label, int32_t* slot) {
-  hipLaunchKernelGGL(dev::dt_bin_kernel, dim3(dt_grid(n * d, 256 * 8, 8192)), dim3(256), 0, st, X,
+  hipLaunchKernelGGL(dev::dt_bin_kernel, dim3(grid_for(n * d, 256 * 8, 8192)), dim3(256), 0, st, X,
                      y, n, d, T, nthr, thr, flags, bins, label, slot);
   return hipGetLastError();
 }
@@ -182,7 +155,7 @@ hipError_t launch_dt_hist(hipStream_t st, const uint8_t* bins, const uint8_t* la
                           const int32_t* slot, int64_t n, int d, int B, int g0, int g,
                           uint32_t* hist) {
   // one workgroup per CU; at least one group of rows for every wave of a workgroup
-  const dim3 grid(dt_grid(n, (dev::kDtHistThreads / 64) * dev::kDtHistWide, 256));
+  const dim3 grid(grid_for(n, (dev::kDtHistThreads / 64) * dev::kDtHistWide, 256));
   const dim3 block(dev::kDtHistThreads);
   const bool lds = (int64_t)g * d * B * 2 <= kDtLdsCounters;
   if (lds && d <= 64)
@@ -197,16 +170,9 @@ hipError_t launch_dt_hist(hipStream_t st, const uint8_t* bins, const uint8_t* la
   return hipGetLastError();
 }
 
-hipError_t launch_dt_route(hipStream_t st, const uint8_t* bins, int64_t n, int d,
-                           const DtDecision* dec, int32_t* slot) {
-  hipLaunchKernelGGL(dev::dt_route_kernel, dim3(dt_grid(n, 256, 4096)), dim3(256), 0, st, bins, n,
-                     d, dec, slot);
-  return hipGetLastError();
-}
-
 hipError_t launch_dt_gather(hipStream_t st, const double* X, int d, const int64_t* idx, int64_t m,
                             double* out) {
-  hipLaunchKernelGGL(dev::dt_gather_kernel, dim3(dt_grid(m * d, 256, 4096)), dim3(256), 0, st, X,
+  hipLaunchKernelGGL(dev::dt_gather_kernel, dim3(grid_for(m * d, 256, 4096)), dim3(256), 0, st, X,
                      d, idx, m, out);
   return hipGetLastError();
 }
@@ -214,7 +180,7 @@ hipError_t launch_dt_gather(hipStream_t st, const double* X, int d, const int64_
 hipError_t launch_dt_predict(hipStream_t st, const double* X, int64_t n, int d,
                              const DtNode* nodes, int n_nodes, double* out) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::dt_predict_kernel, dim3(dt_grid(n, 256, 8192)), dim3(256), 0, st, X, n,
+  hipLaunchKernelGGL(dev::dt_predict_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, X, n,
                      d, nodes, n_nodes, out);
   return hipGetLastError();
 }

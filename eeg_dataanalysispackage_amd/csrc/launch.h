@@ -181,11 +181,18 @@ hipError_t launch_lr_predict(hipStream_t st, int grad, const double* X, int64_t 
                              int use_threshold, double* out);
 
 
-// dtree.hip: the O(n d) passes of the decision tree (eegfx_dtree_*; the host half is dtree_host.h).
-struct DtDecision {   // one active node's outcome of a level, read by dt_route_kernel
+// blocks for `items` at `per_block` a block: at least 1, at most `cap` (grid-stride kernels)
+inline unsigned grid_for(int64_t items, int per_block, int64_t cap) {
+  const int64_t g = (items + per_block - 1) / per_block;
+  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// dtree.hip: the O(n d) passes of the decision tree (eegfx_dtree_*; the host half is dtree_host.h,
+// the driver tree_driver.cpp).
+struct DtDecision {   // one queued node's outcome, read by rf_route_kernel
   int32_t feature;    // -1: the node became a leaf
   int32_t split;      // bins 0..split go left
-  int32_t left, right;  // the children's slots of the next level, -1: leaf
+  int32_t left, right;  // the children's queue tickets, -1: leaf
 };
 struct DtNode {       // one node as dt_predict_kernel walks it
   int32_t feature, left, right, pad;
@@ -205,8 +212,6 @@ hipError_t launch_dt_bin(hipStream_t st, const double* X, const double* y, int64
 hipError_t launch_dt_hist(hipStream_t st, const uint8_t* bins, const uint8_t* label,
                           const int32_t* slot, int64_t n, int d, int B, int g0, int g,
                           uint32_t* hist);
-hipError_t launch_dt_route(hipStream_t st, const uint8_t* bins, int64_t n, int d,
-                           const DtDecision* dec, int32_t* slot);
 // rows idx[0..m) of X, packed
 hipError_t launch_dt_gather(hipStream_t st, const double* X, int d, const int64_t* idx, int64_t m,
                             double* out);
@@ -226,7 +231,9 @@ hipError_t launch_rf_hist(hipStream_t st, const uint8_t* bins, const uint8_t* la
                           const uint8_t* weight, const int32_t* slot, int64_t n, int d, int B,
                           int k, int s0, int g, const int32_t* trees, int nt, const int32_t* sub,
                           uint32_t* hist);
-// dec[g]: the outcome of tickets [s0, s0 + g), left / right = the children's tickets
+// dec[g]: the outcome of tickets [s0, s0 + g), left / right = the children's tickets; rows of other
+// tickets (nodes still queued) keep theirs.  The single unweighted tree: trees -> {0}, nt = 1 and
+// dt_bin_kernel's slot column.
 hipError_t launch_rf_route(hipStream_t st, const uint8_t* bins, int64_t n, int d,
                            const int32_t* trees, int nt, int s0, int g, const DtDecision* dec,
                            int32_t* slot);

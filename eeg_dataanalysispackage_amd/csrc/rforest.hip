@@ -1,6 +1,6 @@
 // rforest.hip -- the O(trees n) passes of train_clf=rf on the GPU: MLlib
 // 1.6.2 RandomForest as Classification/RandomForestClassifier.java:101-136 runs it.  The rows are
-// binned once by dtree.hip's dt_bin_kernel; the host (rforest_driver.cpp over rforest_host.h) draws
+// binned once by dtree.hip's dt_bin_kernel; the host (tree_driver.cpp over rforest_host.h) draws
 // the bagging weights and the feature subsets and chooses every split.  Per tree and row there is
 // a weight (uint8 [tree][row]) and a slot (int32 [tree][row]): the queue ticket of the node the
 // row sits in, -1 when that node is a leaf or the weight is 0.  A group of nodes leaves the queue
@@ -14,12 +14,14 @@
 //                      different nodes, so the lanes of one LDS atomic hit distinct counters.
 //                      Privatised in 128 KB of LDS and merged with integer atomics, non-zero
 //                      counters only; a node too large for LDS adds to global memory directly.
-//   rf_route_kernel    per (tree, row) of the group's trees: slot -> the child's ticket, or -1.
+//   rf_route_kernel    per (tree, row) of the group's trees: slot -> the child's ticket, or -1
+//                      (the single unweighted tree's rows too: one tree, dt_bin_kernel's slots).
 //   rf_predict_kernel  one row per lane walks every tree; 1.0 iff more trees say 1 than 0.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "hist_lds.h"
 #include "launch.h"
 
 namespace eegfx {
@@ -48,10 +50,7 @@ __global__ __launch_bounds__(kRfHistThreads) void rf_hist_kernel(
   __shared__ uint32_t h[LDS ? kDtLdsCounters : 1];
   const int node_counters = k * B * 2;
   const int used = LDS ? g * node_counters : 0;  // <= kDtLdsCounters (launch_rf_hist)
-  if (LDS) {
-    for (int i = threadIdx.x; i < used; i += blockDim.x) h[i] = 0;
-    __syncthreads();
-  }
+  if (LDS) lds_hist_zero(h, used);
   const int lane = threadIdx.x & 63;
   const int waves = (int)blockDim.x >> 6;
   const int pairs = nt * k;
@@ -83,13 +82,7 @@ __global__ __launch_bounds__(kRfHistThreads) void rf_hist_kernel(
       }
     }
   }
-  if (LDS) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < used; i += blockDim.x) {
-      const uint32_t v = h[i];
-      if (v) atomicAdd(&hist[i], v);
-    }
-  }
+  if (LDS) lds_hist_merge(h, used, hist);
 }
 
 __global__ __launch_bounds__(256) void rf_route_kernel(const uint8_t* __restrict__ bins, int64_t n,
@@ -135,14 +128,9 @@ __global__ __launch_bounds__(256) void rf_predict_kernel(const double* __restric
 
 }  // namespace dev
 
-static unsigned rf_grid(int64_t items, int per_block, int64_t cap) {
-  const int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 hipError_t launch_rf_init(hipStream_t st, const uint8_t* weight, int64_t n, int num_trees,
                           int32_t* slot) {
-  const dim3 grid(rf_grid(n, 256 * 4, 1024), rf_grid(num_trees, 1, 1024));
+  const dim3 grid(grid_for(n, 256 * 4, 1024), grid_for(num_trees, 1, 1024));
   hipLaunchKernelGGL(dev::rf_init_kernel, grid, dim3(256), 0, st, weight, n, num_trees, slot);
   return hipGetLastError();
 }
@@ -152,7 +140,7 @@ hipError_t launch_rf_hist(hipStream_t st, const uint8_t* bins, const uint8_t* la
                           int k, int s0, int g, const int32_t* trees, int nt, const int32_t* sub,
                           uint32_t* hist) {
   // one workgroup per CU; at least one block of rows for every wave of a workgroup
-  const dim3 grid(rf_grid(n, (dev::kRfHistThreads / 64) * dev::kRfHistRows, 256));
+  const dim3 grid(grid_for(n, (dev::kRfHistThreads / 64) * dev::kRfHistRows, 256));
   const dim3 block(dev::kRfHistThreads);
   const bool lds = (int64_t)g * k * B * 2 <= kDtLdsCounters;
 #define EEGFX_RF_HIST(L, O)                                                                      \
@@ -171,7 +159,7 @@ hipError_t launch_rf_hist(hipStream_t st, const uint8_t* bins, const uint8_t* la
 hipError_t launch_rf_route(hipStream_t st, const uint8_t* bins, int64_t n, int d,
                            const int32_t* trees, int nt, int s0, int g, const DtDecision* dec,
                            int32_t* slot) {
-  const dim3 grid(rf_grid(n, 256, 2048), rf_grid(nt, 1, 1024));
+  const dim3 grid(grid_for(n, 256, 2048), grid_for(nt, 1, 1024));
   hipLaunchKernelGGL(dev::rf_route_kernel, grid, dim3(256), 0, st, bins, n, d, trees, nt, s0, g,
                      dec, slot);
   return hipGetLastError();
@@ -181,7 +169,7 @@ hipError_t launch_rf_predict(hipStream_t st, const double* X, int64_t n, int d,
                              const DtNode* nodes, const int32_t* offsets, int num_trees,
                              double* out) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::rf_predict_kernel, dim3(rf_grid(n, 256, 8192)), dim3(256), 0, st, X, n,
+  hipLaunchKernelGGL(dev::rf_predict_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, X, n,
                      d, nodes, offsets, num_trees, out);
   return hipGetLastError();
 }

@@ -3,20 +3,19 @@
 // classes), DESIGN.md section 10.2.  The bagging weights (commons-math's PoissonDistribution(1.0)
 // on a Well19937c, one sampler per ParallelCollectionRDD slice), the features of a node
 // (DecisionTreeMetadata, SamplingUtils.reservoirSampleAndCount), the node queue and its groups
-// (RandomForest.selectNodesToSplit), best-split selection over a node's feature list, and the check
-// of a forest before prediction.  No HIP here: rforest_driver.cpp drives the kernels of
-// rforest.hip around these functions, and a stand-alone program can compile them
-// (tests/c_abi/rforest_host_check.cpp).  Thresholds, impurities and the per-node rule are
-// dtree_host.h's.
+// (RandomForest.selectNodesToSplit), and the check of a forest before prediction.  No HIP here:
+// tree_driver.cpp drives the kernels of rforest.hip around these functions, and a stand-alone
+// program can compile them (tests/c_abi/rforest_host_check.cpp).  Thresholds, impurities, split
+// selection and the per-node rule are dtree_host.h's.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
 #include <deque>
-#include <thread>
 #include <vector>
 
 #include "dtree_host.h"
+#include "joiner.h"
 #include "spark_sample.h"
 
 namespace eegfx {
@@ -114,13 +113,7 @@ inline bool poisson_bag(int64_t n, int num_trees, int P, int64_t seed, uint8_t* 
   if (W == 1) {
     work(0);
   } else {
-    struct Join {
-      std::vector<std::thread> th;
-      ~Join() {
-        for (auto& t : th)
-          if (t.joinable()) t.join();
-      }
-    } pool;
+    Joiner pool;
     for (int t = 0; t < W; ++t) pool.th.emplace_back(work, t);
   }
   bool ok = true;
@@ -220,45 +213,8 @@ inline void enqueue_children(const std::vector<QNode>& group, const std::vector<
     }
 }
 
-// binsToBestSplit over a node's feature list: h = uint32 [k][B][2] (list position, bin, label),
-// position j is feature feat[j] (feat == nullptr: feature j) with nthr[feature] splits.  The first
-// maximum in list order then split order; Best::feature is the feature itself.
-inline dtree::Best best_split(const uint32_t* h, int k, int B, const int32_t* feat,
-                              const int32_t* nthr, int kind, int min_instances) {
-  dtree::Best best;
-  for (int b = 0; b < B; ++b) {
-    best.tot[0] += (double)h[b * 2];
-    best.tot[1] += (double)h[b * 2 + 1];
-  }
-  const double imp_tot = dtree::impurity(kind, best.tot[0], best.tot[1]);
-  for (int j = 0; j < k; ++j) {
-    const int f = feat ? feat[j] : j;
-    double l0 = 0, l1 = 0;
-    for (int s = 0; s < nthr[f]; ++s) {
-      l0 += (double)h[((size_t)j * B + s) * 2];
-      l1 += (double)h[((size_t)j * B + s) * 2 + 1];
-      const double r0 = best.tot[0] - l0, r1 = best.tot[1] - l1;
-      const double lc = l0 + l1, rc = r0 + r1;
-      double gain = -DBL_MAX;
-      if (!(lc < (double)min_instances || rc < (double)min_instances)) {
-        const double t = lc + rc;
-        gain = imp_tot - (lc / t) * dtree::impurity(kind, l0, l1) -
-               (rc / t) * dtree::impurity(kind, r0, r1);
-        if (gain < 0.0) gain = -DBL_MAX;
-      }
-      if (best.feature < 0 || gain > best.gain) {
-        best.feature = f;
-        best.split = s;
-        best.gain = gain;
-        best.left[0] = l0;
-        best.left[1] = l1;
-        best.right[0] = r0;
-        best.right[1] = r1;
-      }
-    }
-  }
-  return best;
-}
+// A node's split over its feature list is the tree's rule under its earlier name here
+using dtree::best_split;
 
 // A forest that prediction may walk: the offsets ascend from 0, every tree has a node, and each
 // tree's slice is a valid node array of its own (children relative to its first node).

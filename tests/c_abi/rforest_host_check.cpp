@@ -98,19 +98,17 @@ static int run_split(FILE* f) {
       hist[((size_t)j * B + bin) * 2 + (y[r] == 1.0 ? 1 : 0)] += w[r];
     }
   const dtree::Best b =
-      rforest::best_split(hist.data(), k, B, feat.data(), nthr.data(), kind, min_instances);
+      dtree::best_split(hist.data(), k, B, feat.data(), nthr.data(), kind, min_instances);
   printf("node %d %d %a %a\n", b.feature, b.split, b.gain,
          dtree::impurity(kind, b.tot[0], b.tot[1]));
-  // the identity list is the decision tree's own selection
+  // the identity list is the decision tree's own selection (no list: feature j)
   if (k == d) {
     bool identity = true;
     for (int j = 0; j < k; ++j) identity = identity && feat[j] == j;
     if (identity) {
-      const dtree::Best t = dtree::best_split(hist.data(), d, B, nthr.data(), kind, min_instances);
-      const dtree::Best u =
-          rforest::best_split(hist.data(), k, B, nullptr, nthr.data(), kind, min_instances);
-      printf("same %d\n", t.feature == b.feature && t.split == b.split && t.gain == b.gain &&
-                              u.feature == b.feature && u.split == b.split && u.gain == b.gain);
+      const dtree::Best t =
+          dtree::best_split(hist.data(), d, B, nullptr, nthr.data(), kind, min_instances);
+      printf("same %d\n", t.feature == b.feature && t.split == b.split && t.gain == b.gain);
     }
   }
   return 0;

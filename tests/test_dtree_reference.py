@@ -195,6 +195,52 @@ def test_host_logic_matches_the_restatement(host_check, tmp_path, kind, max_bins
     assert float.fromhex(imp).hex() == float(root["impurity"]).hex()
 
 
+def _growth_case(n, d, what):
+    rng = np.random.default_rng(1000 * n + d)
+    X = rng.standard_normal((n, d))
+    y = (X @ rng.standard_normal(d) + 0.7 * rng.standard_normal(n) > 0).astype(np.float64)
+    if what == "constant column":
+        X[:, 1] = -2.5
+    if what == "one class":
+        y[:] = 1.0
+    return X, y
+
+
+@pytest.mark.parametrize("min_instances", [1, 5])
+@pytest.mark.parametrize("max_depth", [0, 1, 5])
+@pytest.mark.parametrize("kind", ["gini", "entropy"])
+@pytest.mark.parametrize("n,d,what", [(300, 4, "plain"), (257, 7, "plain"),
+                                      (257, 7, "constant column"), (300, 4, "one class")])
+def test_host_growth_matches_the_restatement(host_check, tmp_path, n, d, what, kind, max_depth,
+                                             min_instances):
+    """dtree::best_split and dtree::grow_node grow a whole tree on the CPU from binned rows (the
+    check program counts each node's histogram itself); every node equals the restatement's: the
+    leaf rule, the ids 2 id + side, the order the children are appended in."""
+    X, y = _growth_case(n, d, what)
+    B = 32
+    thr = [R.thresholds(X[:, c], B - 1) for c in range(d)]
+    bins = np.stack([np.searchsorted(np.asarray(thr[c]), X[:, c], side="left") for c in range(d)],
+                    axis=1)
+    case = tmp_path / "grow.txt"
+    with open(case, "w") as f:
+        f.write(f"{0 if kind == 'gini' else 1} {max_depth} {min_instances} {n} {d} {B}\n")
+        for t in thr:
+            f.write(" ".join([str(len(t))] + [float(v).hex() for v in t]) + "\n")
+        for r in range(n):
+            f.write(" ".join(str(int(b)) for b in bins[r]) + " " + float(y[r]).hex() + "\n")
+    lines = _run(host_check, "grow", case)
+    want = R.train(X, y, kind, max_depth=max_depth, max_bins=B,
+                   min_instances_per_node=min_instances)
+    assert len(lines) == len(want)
+    if what != "one class" and max_depth == 5 and min_instances == 1:
+        assert len(want) > 7   # a real tree: several levels, leaves above max_depth among them
+    for line, nd in zip(lines, want):
+        v = line.split()
+        assert [int(x) for x in v[:4]] == [int(nd[k]) for k in ("id", "feature", "left", "right")]
+        assert [float.fromhex(x).hex() for x in v[4:]] == \
+            [float(nd[k]).hex() for k in ("threshold", "predict", "impurity", "gain")]
+
+
 @pytest.mark.parametrize("rows,d,valid", [
     ([(0, 1, 2), (-1, -1, -1), (-1, -1, -1)], 1, 1),
     ([(-1, -1, -1)], 1, 1),

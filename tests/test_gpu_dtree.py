@@ -142,6 +142,47 @@ def test_deep_tree_runs_node_groups(ctx, d):
         assert max_active(t[0], 12) > 3 * (32768 // (d * 32 * 2))
 
 
+def test_one_tree_level_larger_than_a_group(ctx):
+    """1024 features at 256 bins: a node's aggregates are 256 * 2 * 1024 * 8 B = 4 MB, so a group
+    of the node queue (maxMemoryInMB = 256) is 64 nodes, and a level of one tree with more active
+    nodes than that leaves the queue in several groups: routing one group must leave the rows of
+    the nodes still queued alone.  The restatement is too slow at 1024 features to run here, so
+    the tree is held to its own rows instead: X routed down it in numpy.  The features are random
+    bits, the labels random: every candidate halves its node, so the tree stays full.  (Off the
+    device, the restatement on these rows has 89 active nodes at level 7, and 128 with 8 features;
+    Gaussian features under random labels split a few rows off at a time and reach 19.)"""
+    n, d, depth = 2048, 1024, 8
+    rng = np.random.default_rng(29)
+    X = rng.integers(0, 2, (n, d)).astype(np.float64)
+    y = rng.integers(0, 2, n).astype(np.float64)
+    t = clf.dtree_train(ctx, X, y, max_bins=256, max_depth=depth)
+    # dtree::nodes_valid's conditions
+    at, inner = np.arange(len(t)), t["feature"] >= 0
+    assert np.all(t["feature"] >= -1) and np.all(t["feature"] < d)
+    assert np.all(t["left"][~inner] == -1) and np.all(t["right"][~inner] == -1)
+    for side in ("left", "right"):
+        assert np.all(t[side][inner] > at[inner]) and np.all(t[side][inner] < len(t))
+    assert np.array_equal(t["id"][t["left"][inner]], 2 * t["id"][inner])
+    assert np.array_equal(t["id"][t["right"][inner]], 2 * t["id"][inner] + 1)
+    # the class counts of every node, by routing the rows down the tree
+    counts = np.zeros((len(t), 2), dtype=np.int64)
+    where, live, lab = np.zeros(n, dtype=np.int64), np.arange(n), y.astype(np.int64)
+    while live.size:
+        np.add.at(counts, (where[live], lab[live]), 1)
+        live = live[t["feature"][where[live]] >= 0]
+        a = where[live]
+        left = X[live, t["feature"][a]] <= t["threshold"][a]
+        where[live] = np.where(left, t["left"][a], t["right"][a])
+    total = counts.sum(axis=1)
+    assert total[0] == n and np.all(total >= 1)
+    assert np.array_equal(total[t["left"][inner]] + total[t["right"][inner]], total[inner])
+    assert np.array_equal(t["predict"], (counts[:, 1] > counts[:, 0]).astype(np.float64))
+    assert np.array_equal(t["impurity"], R.impurity("gini", counts[:, 0], counts[:, 1]))
+    assert np.array_equal(clf.dtree_predict(ctx, X, t), t["predict"][where])
+    # a level with more nodes that get a histogram than one group holds
+    assert len(t) < 2 ** (depth + 1) and max_active(t, depth) > 64
+
+
 @pytest.mark.parametrize("mi", [1, 5, 300])
 def test_min_instances_per_node(ctx, mi):
     X, y = rows(300, 4, 23)
