@@ -8,7 +8,8 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
 * :class:`DecisionTreeClassifier`, :func:`dtree_train`, :func:`dtree_predict` -- train_clf=dt
 * :class:`RandomForestClassifier`, :func:`rforest_train`, :func:`rforest_predict`,
   :func:`poisson_bag` -- train_clf=rf
-  (the other classifiers live in :mod:`classification`)
+  (the other classifiers live in :mod:`classification`; :func:`pipeline.run_train_clf` is the
+  train/test flow over ``OffLineDataProvider.split`` with the rows resident on the device)
 * :mod:`brainvision` -- native .vhdr/.vmrk reader and marker planner
 """
 from ._lib import EegfxError, LIB_PATH, lib

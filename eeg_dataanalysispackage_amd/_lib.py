@@ -194,6 +194,12 @@ SIGNATURES = {
     "eegfx_odp_num_shards": (c_int, [c_void_p]),
     "eegfx_odp_get_shard": (c_int, [c_void_p, c_int32, POINTER(OdpShard)]),
     "eegfx_shard_span": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
+    "eegfx_java_shuffle": (c_int, [c_int64, c_int64, c_void_p]),
+    "eegfx_gather_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64,
+                                  c_void_p, c_int]),
+    "eegfx_confusion_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int]),
+    "eegfx_odp_split": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int32, c_int32, c_int32,
+                                c_int32, c_void_p, c_void_p, POINTER(c_int64), c_int]),
 }
 
 _lib = None

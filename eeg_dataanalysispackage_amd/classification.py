@@ -321,6 +321,26 @@ def reference_statistics(predictions, labels) -> ClassificationStatistics:
     return ClassificationStatistics(tp, tn, fp, fn)
 
 
+def confusion_counts(ctx: Context, predictions, labels):
+    """(tp, tn, fp, fn) as reference_statistics reads them, counted on the device in one pass
+    (eegfx_confusion_counts): only the four integers come back.  predictions and labels are both
+    host arrays or both device tensors.  Raises IndexError where reference_statistics does (one
+    actual class, or no rows) and EegfxError for a label that is neither 0.0 nor 1.0."""
+    if _is_device(predictions) != _is_device(labels):
+        raise ValueError("predictions and labels must both be host or both be device arrays")
+    p = _contig(predictions, np.float64)
+    a = _contig(labels, np.float64)
+    n = int(p.shape[0])
+    if p.ndim != 1 or a.ndim != 1 or int(a.shape[0]) != n:
+        raise ValueError(f"predictions and labels must be [n], got {tuple(p.shape)} and "
+                         f"{tuple(a.shape)}")
+    counts = np.zeros(4, dtype=np.int64)
+    mem = _mem(p, a)
+    ctx._call(mem, p, lib().eegfx_confusion_counts, ctx.handle, ptr(p), ptr(a), n, ptr(counts),
+              mem)
+    return tuple(int(v) for v in counts)
+
+
 class LogisticRegressionClassifier:
     """IClassifier for train_clf=logreg (LogisticRegressionClassifier.java), GPU-resident."""
 
@@ -358,8 +378,11 @@ class LogisticRegressionClassifier:
         """:85-114 -- the config_* keys select the static train(...) (regParam 0.0), otherwise
         the default LogisticRegressionWithSGD().run (regParam 0.01)."""
         self.fe = fe
-        X = self._features(epochs)
-        y = np.asarray(targets, dtype=np.float64)
+        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
+
+    def trainFeatures(self, X, y) -> None:
+        """train() on feature rows that exist already (host arrays or device tensors, as
+        OffLineDataProvider.split returns them): the same config switches."""
         c = self.config
         if all(k in c for k in ("config_num_iterations", "config_step_size",
                                 "config_mini_batch_fraction")):
@@ -384,6 +407,18 @@ class LogisticRegressionClassifier:
         pred = self.predict(self._features(epochs))
         return reference_statistics(pred, targets)
 
+    def testFeatures(self, X, y) -> ClassificationStatistics:
+        """test() on feature rows that exist already.  Predictions of device rows stay on the
+        device and are counted there (confusion_counts: four integers come back); host rows go
+        through reference_statistics as test() does."""
+        pred = self.predict(X)
+        if not _is_device(pred):
+            return reference_statistics(pred, y)
+        if not _is_device(y):
+            import torch
+            y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float64), device=pred.device)
+        return ClassificationStatistics(*confusion_counts(self.context, pred, y))
+
 
 class SVMClassifier(LogisticRegressionClassifier):
     """IClassifier for train_clf=svm (SVMClassifier.java), GPU-resident: the same flow as
@@ -395,8 +430,9 @@ class SVMClassifier(LogisticRegressionClassifier):
         regParam, fraction); otherwise new SVMWithSGD().run (step 1.0, 100 iterations,
         regParam 0.01, fraction 1.0)."""
         self.fe = fe
-        X = self._features(epochs)
-        y = np.asarray(targets, dtype=np.float64)
+        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
+
+    def trainFeatures(self, X, y) -> None:
         c = self.config
         if all(k in c for k in ("config_num_iterations", "config_step_size", "config_reg_param",
                                 "config_mini_batch_fraction")):
@@ -442,8 +478,9 @@ class DecisionTreeClassifier(LogisticRegressionClassifier):
         config_min_instances_per_node all set, those instead ("gini" is Gini, any other string
         Entropy)."""
         self.fe = fe
-        X = self._features(epochs)
-        y = np.asarray(targets, dtype=np.float64)
+        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
+
+    def trainFeatures(self, X, y) -> None:
         c = self.config
         kw = _tree_config(c) if all(k in c for k in self.CONFIG_KEYS) else {}
         self.nodes = dtree_train(self.context, X, y, split_seed=self.split_seed, **kw)
@@ -476,8 +513,9 @@ class RandomForestClassifier(DecisionTreeClassifier):
         with all six config keys set, their values instead ("gini" is Gini, any other string
         Entropy; a feature subset that is no strategy's name is Spark's failed require)."""
         self.fe = fe
-        X = self._features(epochs)
-        y = np.asarray(targets, dtype=np.float64)
+        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
+
+    def trainFeatures(self, X, y) -> None:
         c = self.config
         kw = {}
         if all(k in c for k in self.CONFIG_KEYS):
@@ -497,6 +535,6 @@ class RandomForestClassifier(DecisionTreeClassifier):
 
 
 __all__ = ["ClassificationStatistics", "DecisionTreeClassifier", "LogisticRegressionClassifier",
-           "RandomForestClassifier", "SVMClassifier", "dtree_predict", "dtree_train",
-           "poisson_bag", "predict", "reference_statistics", "rforest_predict", "rforest_train",
-           "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]
+           "RandomForestClassifier", "SVMClassifier", "confusion_counts", "dtree_predict",
+           "dtree_train", "poisson_bag", "predict", "reference_statistics", "rforest_predict",
+           "rforest_train", "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]

@@ -1,6 +1,7 @@
 // ctx.h -- the device context (struct eegfx_ctx) and the helpers that the host sources share:
 // the argument checks (defined in api.cpp) and the device-pointer pipelines (routes.cpp), used by
-// api.cpp, streamed.cpp, classify.cpp, mailbox.cpp and odp.cpp (the OffLineDataProvider).
+// api.cpp, streamed.cpp, classify.cpp, mailbox.cpp, flow.cpp and odp.cpp (the
+// OffLineDataProvider).
 // Internal: not installed.
 #pragma once
 
@@ -172,6 +173,9 @@ struct eegfx_ctx {
   // the random forest (eegfx_rforest_*) on top of them: weight per tree and row, slot per tree and
   // row, a group's feature subsets and launch tree lists / the tree offsets of a prediction
   DevBuf rf_weight, rf_slot, rf_tab;
+  // the train/test flow (flow.cpp, eegfx_odp_split): rows to gather from / predictions, the
+  // indices, the gathered rows, labels in, labels out, and the kernels' flag / counter block
+  DevBuf fl_src, fl_idx, fl_dst, fl_lab, fl_y, fl_flag;
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
   PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
                                          // a sharded provider's worker: the file spans it reads
@@ -201,13 +205,15 @@ struct eegfx_ctx {
   void bind_buffers() {
     for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
                       &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec,
-                      &rf_weight, &rf_slot, &rf_tab})
+                      &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
+                      &fl_flag})
       b->sp = &stream;
   }
   void release_buffers() {
     for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
                       &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec,
-                      &rf_weight, &rf_slot, &rf_tab})
+                      &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
+                      &fl_flag})
       b->release();
     pin_in.release();
     pin_out.release();
@@ -344,6 +350,13 @@ struct DtBinned {
 };
 void dt_bin_rows(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
                  int32_t max_bins, int64_t split_seed, int mem, size_t hist_bytes, DtBinned* out);
+// flow.cpp: Collections.shuffle(list, new Random(seed)) of n items as the original index of every
+// position, and the row gather on the context stream (device pointers, m > 0, timed): `slot`
+// (0 or 1) picks the word of ctx->fl_flag that gather_check reads after the stream has drained.
+std::vector<int64_t> java_shuffle(int64_t n, int64_t seed);
+void run_gather_rows(eegfx_ctx* ctx, const double* src, int64_t n_src, int d, const int64_t* idx,
+                     int64_t m, double* dst, int slot);
+void gather_check(eegfx_ctx* ctx, int slots, int64_t n_src);
 // The raw entries' argument ladder up to the null-buffer check (api.cpp check_raw_args goes on
 // from it).  `mem`: EEGFX_MEM_HOST from an entry without a mem flag.
 void check_raw_head(const eegfx_ctx* ctx, int mem, const void* raw, int fmt, int64_t n_frames,

@@ -242,4 +242,25 @@ hipError_t launch_rf_predict(hipStream_t st, const double* X, int64_t n, int d,
                              const DtNode* nodes, const int32_t* offsets, int num_trees,
                              double* out);
 
+// flow.hip: the train/test flow's row gather and confusion counts (eegfx_gather_rows,
+// eegfx_confusion_counts, eegfx_odp_split).
+constexpr int kGatherMaxD = 1536;      // 3 channels x the extractor's largest feature size
+constexpr int kGatherThreads = 256;
+constexpr int kGatherUnroll = 4;       // pieces a thread moves per trip of its grid-stride loop
+constexpr int kGatherMaxBlocks = 2048;  // 8 workgroups for each of the 256 CUs
+// dst[i][0:d] = src[idx[i]][0:d] for i < m, bits copied; 16-byte pieces when d is even and src
+// and dst lie on 16-byte boundaries, else 8-byte pieces.  An idx[i] outside [0, n_src) copies
+// nothing for row i and lowers *bad (set to ~0 by the caller) to the smallest such i.
+hipError_t launch_gather_rows(hipStream_t st, const double* src, int64_t n_src, int d,
+                              const int64_t* idx, int64_t m, double* dst, unsigned long long* bad);
+constexpr int kConfusionThreads = 256;
+constexpr unsigned kSeenZero = 1, kSeenOne = 2, kSeenOther = 4;
+struct ConfusionOut {          // zeroed by the caller
+  unsigned long long cell[4];  // tp, tn, fp, fn as classification.reference_statistics reads them
+  unsigned seen;               // kSeen* of the labels: 0.0, 1.0, anything else
+  unsigned pad;
+};
+hipError_t launch_confusion(hipStream_t st, const double* pred, const double* labels, int64_t n,
+                            ConfusionOut* out);
+
 }  // namespace eegfx

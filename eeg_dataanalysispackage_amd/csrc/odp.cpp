@@ -453,6 +453,26 @@ struct eegfx_odp {
     }
     if (first) throw *first;
   }
+
+  // getFeatures on every shard: the rows computed with the epochs at loadData when they are the
+  // ones asked for (the one-pass kernels), else the batch extract over the resident epochs;
+  // `land(ctx, shard, rows, bytes)` enqueues their copy to where the caller wants them.
+  template <typename F>
+  void feature_rows(int32_t skip, int32_t feature_size, F&& land) const {
+    const size_t row = sizeof(double) * 3 * (size_t)feature_size;
+    on_shards([&](eegfx_ctx* ctx, const Shard& s) {
+      const size_t bytes = row * (size_t)s.count;
+      if (skip == EEGFX_DWT8_SKIP && feature_size == EEGFX_DWT8_FEATURE_SIZE &&
+          s.numerics == ctx->numerics && s.d_features) {
+        land(ctx, s, (const double*)s.d_features, bytes);
+        return;
+      }
+      double* d_out = (double*)ctx->out.get(bytes);
+      run_features_from_epochs(ctx, (const double*)s.d_epochs, s.count, 3, skip, feature_size,
+                               d_out, EEGFX_POSTSTIMULUS);
+      land(ctx, s, d_out, bytes);
+    });
+  }
 };
 
 extern "C" {
@@ -533,20 +553,67 @@ int eegfx_odp_get_features(eegfx_odp* odp, int32_t name, int32_t epoch_size, int
     check_fe_params(3, name, epoch_size, skip, feature_size);
     if (!odp->n_epochs) return;
     const size_t row = sizeof(double) * 3 * (size_t)feature_size;
-    odp->on_shards([&](eegfx_ctx* ctx, const eegfx_odp::Shard& s) {
-      char* dst = (char*)out + row * (size_t)s.first;
-      const size_t bytes = row * (size_t)s.count;
-      if (skip == EEGFX_DWT8_SKIP && feature_size == EEGFX_DWT8_FEATURE_SIZE &&
-          s.numerics == ctx->numerics && s.d_features) {
-        // the rows computed with the epochs at loadData (the one-pass kernels)
-        HIP_CHECK(hipMemcpyAsync(dst, s.d_features, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        return;
-      }
-      double* d_out = (double*)ctx->out.get(bytes);
-      run_features_from_epochs(ctx, (const double*)s.d_epochs, s.count, 3, skip, feature_size,
-                               d_out, EEGFX_POSTSTIMULUS);
-      HIP_CHECK(hipMemcpyAsync(dst, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    odp->feature_rows(skip, feature_size, [&](eegfx_ctx* ctx, const eegfx_odp::Shard& s,
+                                              const double* rows, size_t bytes) {
+      HIP_CHECK(hipMemcpyAsync((char*)out + row * (size_t)s.first, rows, bytes,
+                               hipMemcpyDeviceToHost, ctx->stream));
     });
+  });
+}
+
+int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_fraction,
+                    int32_t name, int32_t epoch_size, int32_t skip, int32_t feature_size,
+                    double* X, double* y, int64_t* n_train, int mem) {
+  return guarded([&] {
+    if (!odp || !n_train) fail(EEGFX_EINVAL, "null argument");
+    check_mem(mem);
+    if (!(train_fraction >= 0.0 && train_fraction <= 1.0))
+      fail(EEGFX_EINVAL, "train_fraction %g outside [0, 1]", train_fraction);
+    check_fe_params(3, name, epoch_size, skip, feature_size);
+    if (odp->ctxs.empty())
+      fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
+    if (!ctx) ctx = odp->ctxs[0];
+    const int64_t n = odp->n_epochs;
+    *n_train = (int64_t)((double)n * train_fraction);  // (int)(data.size()*0.7)
+    if (n == 0) return;
+    if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
+    const std::vector<int64_t> perm = java_shuffle(n, seed);
+    const int d = 3 * feature_size;
+    const size_t row = sizeof(double) * (size_t)d;
+    // every row in list order in one buffer on ctx; the allocations are complete before another
+    // context's stream writes there
+    ctx->activate();
+    char* rows = (char*)ctx->fl_src.get(row * (size_t)n);
+    int64_t* d_perm = (int64_t*)ctx->fl_idx.get(sizeof(int64_t) * (size_t)n);
+    double* d_lab = (double*)ctx->fl_lab.get(sizeof(double) * (size_t)n);
+    double* d_X = X;
+    double* d_y = y;
+    if (mem == EEGFX_MEM_HOST) {
+      d_X = (double*)ctx->fl_dst.get(row * (size_t)n);
+      d_y = (double*)ctx->fl_y.get(sizeof(double) * (size_t)n);
+    }
+    ctx->drain();
+    odp->feature_rows(skip, feature_size, [&](eegfx_ctx* c, const eegfx_odp::Shard& s,
+                                              const double* from, size_t bytes) {
+      char* dst = rows + row * (size_t)s.first;
+      if (c->device == ctx->device)
+        HIP_CHECK(hipMemcpyAsync(dst, from, bytes, hipMemcpyDeviceToDevice, c->stream));
+      else
+        HIP_CHECK(hipMemcpyPeerAsync(dst, ctx->device, from, c->device, bytes, c->stream));
+    });
+    ctx->activate();
+    HIP_CHECK(hipMemcpyAsync(d_lab, odp->labels.data(), sizeof(double) * (size_t)n,
+                             hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(d_perm, perm.data(), sizeof(int64_t) * (size_t)n,
+                             hipMemcpyHostToDevice, ctx->stream));
+    run_gather_rows(ctx, (const double*)rows, n, d, d_perm, n, d_X, 0);
+    run_gather_rows(ctx, d_lab, n, 1, d_perm, n, d_y, 1);
+    if (mem == EEGFX_MEM_HOST) {
+      HIP_CHECK(hipMemcpyAsync(X, d_X, row * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(y, d_y, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    }
+    gather_check(ctx, 2, n);
   });
 }
 

@@ -159,6 +159,43 @@ class OffLineDataProvider:
                                                ctypes.c_void_p(out.ctypes.data)))
         return out
 
+    def split(self, fe=None, seed: int = 1, train_fraction: float = 0.7, device: bool = True,
+              context: Optional[Context] = None):
+        """The train/test data of PipelineBuilder.execute (:177-187) without a trip through host
+        memory (eegfx_odp_split): the rows of getFeatures(fe's parameters) and the labels, both
+        in the order of Collections.shuffle(list, new Random(seed)), cut at
+        int(n * train_fraction).  Returns (X_train, y_train, X_test, y_test): with device=True
+        torch tensors on the context's device (views of one allocation), otherwise numpy arrays.
+        fe: a WaveletTransform (default (8, 512, 175, 16)); context: where the rows land (default
+        the provider's first context)."""
+        name, size, skip, fs = ((8, 512, 175, 16) if fe is None else
+                                (fe.NAME, fe.EPOCH_SIZE, fe.SKIP_SAMPLES, fe.FEATURE_SIZE))
+        n_train = ctypes.c_int64()
+
+        def call(ctx, X, y, mem):
+            args = (self._h, None if ctx is None else ctx.handle, int(seed), float(train_fraction),
+                    int(name), int(size), int(skip), int(fs), _lib.ptr(X), _lib.ptr(y),
+                    ctypes.byref(n_train), mem)
+            if mem == _lib.MEM_DEVICE:
+                ctx._call(mem, X, lib().eegfx_odp_split, *args)
+            else:
+                check(lib().eegfx_odp_split(*args))
+
+        if not self._ctxs:  # planning-only: the library's refusal
+            call(None, None, None, _lib.MEM_HOST)
+        ctx = context if context is not None else self._ctxs[0]
+        n, d = self.num_epochs(), 3 * max(int(fs), 0)
+        if device:
+            import torch
+            buf = torch.empty(n * (d + 1), dtype=torch.float64, device=f"cuda:{ctx.device}")
+            X, y = buf[:n * d].view(n, d), buf[n * d:]
+            call(ctx, X, y, _lib.MEM_DEVICE)
+        else:
+            X, y = np.empty((n, d), dtype=np.float64), np.empty(n, dtype=np.float64)
+            call(ctx, X, y, _lib.MEM_HOST)
+        cut = int(n_train.value)
+        return X[:cut], y[:cut], X[cut:], y[cut:]
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:
             lib().eegfx_odp_destroy(self._h)

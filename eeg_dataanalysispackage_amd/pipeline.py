@@ -9,6 +9,10 @@ same train/test split the reference uses:
 * ``subList(0, (int)(size*0.7))`` / ``subList((int)(size*0.7), size)`` (:182-187);
 * ``featureExtractionFunc`` + ``zip`` into ``LabeledPoint(label, features)``
   (Classification/LogisticRegressionClassifier.java:55-68, :87-94), batched on the device.
+
+``run_train_clf`` is the whole ``train_clf`` branch (:170-223) with the rows resident on the device
+from the provider to the four counters (``OffLineDataProvider.split``, ``trainFeatures``,
+``testFeatures``); ``native_shuffle`` and ``gather_rows`` are its pieces over the C ABI.
 """
 from __future__ import annotations
 
@@ -82,3 +86,56 @@ def train_test_features(odp, fe) -> Tuple[np.ndarray, List[float], np.ndarray, L
     ftr = fe.extractFeaturesBatch(np.ascontiguousarray(data[tr])) if tr else np.empty((0, 48))
     fte = fe.extractFeaturesBatch(np.ascontiguousarray(data[te])) if te else np.empty((0, 48))
     return ftr, [labels[i] for i in tr], fte, [labels[i] for i in te]
+
+
+def native_shuffle(n: int, seed: int = 1) -> np.ndarray:
+    """java_shuffle_permutation(n, seed) by the library (eegfx_java_shuffle, host only), as
+    int64[n]."""
+    from ._lib import check, lib, ptr
+    perm = np.empty(max(int(n), 0), dtype=np.int64)
+    check(lib().eegfx_java_shuffle(int(n), int(seed), ptr(perm)))
+    return perm
+
+
+def gather_rows(ctx, src, idx, out=None):
+    """out[i] = src[idx[i]] on the device (eegfx_gather_rows), bits copied.  src: float64 [n][d]
+    with 1 <= d <= 1536, or [n] (d = 1); idx: int64 [m], may repeat; all host arrays or all device
+    tensors.  An index outside [0, n) raises IndexError and leaves that row of out alone."""
+    from ._lib import lib, ptr
+    from .context import _check_out, _contig, _empty_like_mem, _mem
+    src = _contig(src, np.float64)
+    idx = _contig(idx, np.int64)
+    if src.ndim not in (1, 2) or idx.ndim != 1:
+        raise ValueError(f"src must be [n][d] or [n] and idx [m], got {tuple(src.shape)} and "
+                         f"{tuple(idx.shape)}")
+    n, m = int(src.shape[0]), int(idx.shape[0])
+    d = int(src.shape[1]) if src.ndim == 2 else 1
+    shape = (m, d) if src.ndim == 2 else (m,)
+    if out is None:
+        out = _empty_like_mem(src, shape, "float64")
+    _check_out(out, shape)
+    mem = _mem(src, idx, out)
+    ctx._call(mem, src, lib().eegfx_gather_rows, ctx.handle, ptr(src), n, d, ptr(idx), m,
+              ptr(out), mem)
+    return out
+
+
+def run_train_clf(odp, classifier, fe=None):
+    """PipelineBuilder.execute's train_clf branch (:170-223) for a loaded provider and one of the
+    classifiers of :mod:`classification` (its config set by the caller): shuffle with Random(1),
+    split 70/30, train, test; returns the ClassificationStatistics.  Epochs and feature rows stay
+    on the device: what reaches the host is the model (and the tree's threshold sample) and the
+    four counters.  ``fe``: a WaveletTransform, default (8, 512, 175, 16).  A classifier without
+    a context of its own runs on the provider's first one."""
+    from .feature_extraction import WaveletTransform
+    if fe is None:
+        fe = WaveletTransform(8, 512, 175, 16)
+    ctx = classifier._ctx
+    if ctx is None and odp._ctxs:
+        ctx = odp._ctxs[0]
+    x_train, y_train, x_test, y_test = odp.split(fe, device=True, context=ctx)
+    if classifier._ctx is None:
+        classifier._ctx = ctx
+    classifier.setFeatureExtraction(fe)
+    classifier.trainFeatures(x_train, y_train)
+    return classifier.testFeatures(x_test, y_test)

@@ -604,6 +604,48 @@ int eegfx_odp_get_shard(const eegfx_odp* odp, int32_t i, eegfx_odp_shard* out);
 int eegfx_shard_span(const int64_t* pos, int64_t n, int64_t n_frames, int64_t* first_frame,
                      int64_t* frames);
 
+/* ---- the train/test flow (PipelineBuilder.java:170-223) on the device ------------------------
+ * The train_clf branch shuffles the epochs and the labels with Random(1), splits 70/30, trains,
+ * tests and reports four counters.  These entries keep the feature rows on the device from the
+ * provider's shards to the classifiers.
+ *
+ * eegfx_java_shuffle (pure host function): perm[i] is the original index of the element at
+ * position i after Collections.shuffle(list, new Random(seed)) of a list of n items.  n outside
+ * [0, 2^31) is EEGFX_EINVAL.
+ *
+ * eegfx_gather_rows: dst[i][0:d] = src[idx[i]][0:d] for i < m, rows of 1 <= d <= 1536 doubles
+ * copied as bits (NaN payloads and -0.0 survive), idx may repeat; src [n_src][d], idx and dst
+ * [m][d] all live on the side `mem` names and need only 8-byte alignment.  An idx[i] outside
+ * [0, n_src) copies nothing for row i; the call then returns EEGFX_ERANGE and names the smallest
+ * such i (host memory: that row keeps what dst held).  m == 0 is EEGFX_OK without a launch.
+ * The call synchronises.
+ *
+ * eegfx_confusion_counts: counts = {tp, tn, fp, fn} of pred[n] against labels[n] in the
+ * reference's reading of MulticlassMetrics' column-major matrix (LogisticRegressionClassifier
+ * .java:129-137): tp = actual 1 / predicted 1, tn = actual 0 / predicted 0, "fp" = actual 1 /
+ * predicted 0, "fn" = actual 0 / predicted 1.  A prediction that is neither 0.0 nor 1.0 (NaN, a
+ * raw score) is counted nowhere.  A label that is neither 0.0 nor 1.0 is EEGFX_EINVAL (checked
+ * first); labels of one class only, or n == 0, are EEGFX_ERANGE: the reference's cm[1] throws.
+ * `counts` is host memory; `mem` names the side of pred and labels.  The call synchronises.
+ *
+ * eegfx_odp_split: X[n][3 * feature_size] = the provider's feature rows (eegfx_odp_get_features
+ * with the same parameters, bit for bit) and y[n] = its labels, both in the order
+ * eegfx_java_shuffle(n, seed) gives; rows [0, *n_train) are the training part, *n_train =
+ * (int64_t)(n * train_fraction) as (int)(data.size()*0.7) truncates.  `mem` names the side of X
+ * and y; device buffers live on ctx's device (ctx == NULL: the provider's first context).  Every
+ * shard lands its rows in a buffer of ctx by a device-to-device copy on its own stream; the
+ * gathers for X and y then run on ctx's stream, so no row passes through host memory.
+ * train_fraction outside [0, 1] and a planning-only provider are EEGFX_EINVAL; n == 0 is
+ * EEGFX_OK with *n_train = 0.  The call synchronises. */
+int eegfx_java_shuffle(int64_t n, int64_t seed, int64_t* perm);
+int eegfx_gather_rows(eegfx_ctx* ctx, const double* src, int64_t n_src, int32_t d,
+                      const int64_t* idx, int64_t m, double* dst, int mem);
+int eegfx_confusion_counts(eegfx_ctx* ctx, const double* pred, const double* labels, int64_t n,
+                           int64_t counts[4], int mem);
+int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_fraction,
+                    int32_t name, int32_t epoch_size, int32_t skip, int32_t feature_size,
+                    double* X, double* y, int64_t* n_train, int mem);
+
 #ifdef __cplusplus
 }
 #endif
