@@ -35,19 +35,39 @@ DEFAULT_MINI_BATCH_FRACTION = 1.0
 CONVERGENCE_TOL = 0.001
 
 
-def _train(entry, ctx: Context, X, y, num_iterations, step_size, reg_param, mini_batch_fraction,
-           convergence_tol, initial_weights, num_partitions=None):
+def _train_inputs(X, y):
+    """The (X, y) of every train call: contiguous float64 [n][d] and [n] on one side.  Returns
+    them with n, d and the mem flag."""
     if _is_device(X) != _is_device(y):
         raise ValueError("X and y must both be host or both be device arrays")
     X = _contig(X, np.float64)
     y = _contig(y, np.float64)
-    n, d = int(X.shape[0]), int(X.shape[1])
-    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != n:
+    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
         raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
+    return X, y, int(X.shape[0]), int(X.shape[1]), _mem(X, y)
+
+
+def _predict_inputs(X):
+    """The X of every predict call: contiguous float64 [n][d].  Returns it with the output (one
+    float64 per row on X's side: a torch tensor on its device, else numpy), the mem flag, n, d."""
+    X = _contig(X, np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if _is_device(X):
+        import torch
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    else:
+        out = np.empty(n, dtype=np.float64)
+    return X, out, _mem(X, out), n, d
+
+
+def _train(entry, ctx: Context, X, y, num_iterations, step_size, reg_param, mini_batch_fraction,
+           convergence_tol, initial_weights, num_partitions=None):
+    X, y, n, d, mem = _train_inputs(X, y)
     w = (np.zeros(d) if initial_weights is None
          else np.array(initial_weights, dtype=np.float64).copy())
     it = c_int32()
-    mem = _mem(X, y)
     # ordered after the torch work that produced X / y (Context._call), like every device call
     head = (ctx.handle, ptr(X), ptr(y), n, d, int(num_iterations), float(step_size),
             float(reg_param), float(mini_batch_fraction), float(convergence_tol))
@@ -59,22 +79,10 @@ def _train(entry, ctx: Context, X, y, num_iterations, step_size, reg_param, mini
     return w, it.value
 
 
-def _predict_out(X):
-    """One float64 per row of X, on X's side (a torch tensor on its device, else numpy)."""
-    n = int(X.shape[0])
-    if _is_device(X):
-        import torch
-        return torch.empty(n, dtype=torch.float64, device=X.device)
-    return np.empty(n, dtype=np.float64)
-
-
 def _predict(entry, ctx: Context, X, weights, intercept, threshold):
     w = np.ascontiguousarray(weights, dtype=np.float64)
-    X = _contig(X, np.float64)
-    n, d = int(X.shape[0]), int(X.shape[1])
-    out = _predict_out(X)
+    X, out, mem, n, d = _predict_inputs(X)
     t = math.nan if threshold is None else float(threshold)
-    mem = _mem(X, out)
     ctx._call(mem, X, getattr(lib(), entry), ctx.handle, ptr(X), n, d, ptr(w), float(intercept),
               t, ptr(out), mem)
     return out
@@ -140,19 +148,11 @@ DEFAULT_MIN_INSTANCES_PER_NODE = 1
 TREE_NODE = np.dtype(_lib.TreeNode)
 
 
-def _tree_inputs(X, y, impurity):
-    """The checks dtree_train and rforest_train share: (X, y) contiguous float64 [n][d] and [n] on
-    one side, and the impurity's code."""
+def _impurity(impurity):
     kinds = {"gini": _lib.GINI, "entropy": _lib.ENTROPY}
     if impurity not in kinds:
         raise ValueError(f"impurity must be one of {sorted(kinds)}, got {impurity!r}")
-    if _is_device(X) != _is_device(y):
-        raise ValueError("X and y must both be host or both be device arrays")
-    X = _contig(X, np.float64)
-    y = _contig(y, np.float64)
-    if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
-        raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and {tuple(y.shape)}")
-    return X, y, kinds[impurity]
+    return kinds[impurity]
 
 
 def dtree_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
@@ -165,14 +165,13 @@ def dtree_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
     X (n x d float64, host numpy or device torch) and y (n labels 0/1) may live on either side.
     impurity: "gini" or "entropy".  split_seed seeds the Bernoulli sample of the rows the
     thresholds come from when n > max(max_bins^2, 10000) (Spark draws it fresh on every run)."""
-    X, y, kind = _tree_inputs(X, y, impurity)
-    n, d = int(X.shape[0]), int(X.shape[1])
+    kind = _impurity(impurity)
+    X, y, n, d, mem = _train_inputs(X, y)
     # every leaf holds a row and no node lies below max_depth
     depth = min(max(int(max_depth), 0), 30)
     capacity = max(1, min(2 ** (depth + 1) - 1, 2 * n - 1))
     nodes = np.zeros(capacity, dtype=TREE_NODE)
     count = c_int32()
-    mem = _mem(X, y)
     ctx._call(mem, X, lib().eegfx_dtree_train, ctx.handle, ptr(X), ptr(y), n, d, kind,
               int(max_depth), int(max_bins), int(min_instances_per_node), int(split_seed),
               ptr(nodes), capacity, byref(count), mem)
@@ -183,12 +182,7 @@ def dtree_predict(ctx: Context, X, nodes):
     """DecisionTreeModel.predict on the device (eegfx_dtree_predict): the 0/1 of the leaf each row
     of X (host numpy or device torch) reaches; left iff x[feature] <= threshold."""
     nodes = np.ascontiguousarray(nodes, dtype=TREE_NODE)
-    X = _contig(X, np.float64)
-    if X.ndim != 2:
-        raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
-    n, d = int(X.shape[0]), int(X.shape[1])
-    out = _predict_out(X)
-    mem = _mem(X, out)
+    X, out, mem, n, d = _predict_inputs(X)
     ctx._call(mem, X, lib().eegfx_dtree_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
               int(nodes.shape[0]), ptr(out), mem)
     return out
@@ -216,18 +210,17 @@ def rforest_train(ctx: Context, X, y, impurity: str = DEFAULT_IMPURITY,
     num_partitions the slices of the training RDD the bagging samplers belong to (None: the
     processors available to the process, as for sgd_train); the other arguments are dtree_train's.
     num_trees = 1 with "auto" or "all" is dtree_train's tree."""
-    X, y, kind = _tree_inputs(X, y, impurity)
+    kind = _impurity(impurity)
+    X, y, n, d, mem = _train_inputs(X, y)
     if feature_subset not in FEATURE_SUBSETS:
         raise ValueError(f"feature_subset must be one of {sorted(FEATURE_SUBSETS)}, "
                          f"got {feature_subset!r}")
-    n, d = int(X.shape[0]), int(X.shape[1])
     trees = max(int(num_trees), 1)
     depth = min(max(int(max_depth), 0), 30)
     # a first guess; the call reports the count needed when the forest is larger
     capacity = max(1, trees * min(2 ** (depth + 1) - 1, 2 * n - 1, 1023))
     offsets = np.zeros(trees + 1, dtype=np.int32)
     count = c_int32()
-    mem = _mem(X, y)
     while True:
         nodes = np.zeros(capacity, dtype=TREE_NODE)
         count.value = 0
@@ -252,12 +245,7 @@ def rforest_predict(ctx: Context, X, nodes, tree_offsets):
     offsets = np.ascontiguousarray(tree_offsets, dtype=np.int32)
     if offsets.ndim != 1 or offsets.shape[0] < 2 or int(offsets[-1]) != int(nodes.shape[0]):
         raise ValueError("tree_offsets must hold one offset per tree and end at len(nodes)")
-    X = _contig(X, np.float64)
-    if X.ndim != 2:
-        raise ValueError(f"X must be [n][d], got {tuple(X.shape)}")
-    n, d = int(X.shape[0]), int(X.shape[1])
-    out = _predict_out(X)
-    mem = _mem(X, out)
+    X, out, mem, n, d = _predict_inputs(X)
     ctx._call(mem, X, lib().eegfx_rforest_predict, ctx.handle, ptr(X), n, d, ptr(nodes),
               ptr(offsets), int(offsets.shape[0]) - 1, ptr(out), mem)
     return out
@@ -341,16 +329,15 @@ def confusion_counts(ctx: Context, predictions, labels):
     return tuple(int(v) for v in counts)
 
 
-class LogisticRegressionClassifier:
-    """IClassifier for train_clf=logreg (LogisticRegressionClassifier.java), GPU-resident."""
+class _Classifier:
+    """What the four IClassifiers share: the context, the feature extraction, the config, and the
+    train / test flow around a subclass's trainFeatures, _trained and _predict_rows."""
 
     def __init__(self, context: Optional[Context] = None):
         self._ctx = context
         self.fe = None
         self.config: Dict[str, str] = {}
-        self.weights: Optional[np.ndarray] = None
-        self.iterations_run = 0
-        # Spark partitions of the training RDD (mini-batch sampling only); None = local[*]
+        # Spark partitions of the training RDD (mini-batch sampling, bagging); None = local[*]
         self.num_partitions: Optional[int] = None
 
     @property
@@ -375,37 +362,20 @@ class LogisticRegressionClassifier:
         return self.fe.extractFeaturesBatch(ep)
 
     def train(self, epochs, targets: Sequence[float], fe) -> None:
-        """:85-114 -- the config_* keys select the static train(...) (regParam 0.0), otherwise
-        the default LogisticRegressionWithSGD().run (regParam 0.01)."""
+        """IClassifier.train: the features of the epochs (one batched device call), then
+        trainFeatures, whose docstring names the reference lines and the config switches."""
         self.fe = fe
         self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
 
-    def trainFeatures(self, X, y) -> None:
-        """train() on feature rows that exist already (host arrays or device tensors, as
-        OffLineDataProvider.split returns them): the same config switches."""
-        c = self.config
-        if all(k in c for k in ("config_num_iterations", "config_step_size",
-                                "config_mini_batch_fraction")):
-            self.weights, self.iterations_run = sgd_train(
-                self.context, X, y, num_iterations=int(c["config_num_iterations"]),
-                step_size=float(c["config_step_size"]), reg_param=0.0,
-                mini_batch_fraction=float(c["config_mini_batch_fraction"]),
-                num_partitions=self.num_partitions)
-        else:
-            self.weights, self.iterations_run = sgd_train(
-                self.context, X, y, DEFAULT_NUM_ITERATIONS, DEFAULT_STEP_SIZE, DEFAULT_REG_PARAM,
-                DEFAULT_MINI_BATCH_FRACTION)
-
     def predict(self, features) -> np.ndarray:
-        if self.weights is None:
+        if not self._trained():
             raise RuntimeError("The classifier has not been trained")  # IllegalStateException
-        return predict(self.context, features, self.weights)
+        return self._predict_rows(features)
 
     def test(self, epochs, targets: Sequence[float]) -> ClassificationStatistics:
-        if self.weights is None:
+        if not self._trained():
             raise RuntimeError("The classifier has not been trained")
-        pred = self.predict(self._features(epochs))
-        return reference_statistics(pred, targets)
+        return reference_statistics(self.predict(self._features(epochs)), targets)
 
     def testFeatures(self, X, y) -> ClassificationStatistics:
         """test() on feature rows that exist already.  Predictions of device rows stay on the
@@ -420,19 +390,48 @@ class LogisticRegressionClassifier:
         return ClassificationStatistics(*confusion_counts(self.context, pred, y))
 
 
-class SVMClassifier(LogisticRegressionClassifier):
-    """IClassifier for train_clf=svm (SVMClassifier.java), GPU-resident: the same flow as
-    LogisticRegressionClassifier with SVMWithSGD and SVMModel.predict."""
+class LogisticRegressionClassifier(_Classifier):
+    """IClassifier for train_clf=logreg (LogisticRegressionClassifier.java), GPU-resident."""
 
-    def train(self, epochs, targets: Sequence[float], fe) -> None:
+    def __init__(self, context: Optional[Context] = None):
+        super().__init__(context)
+        self.weights: Optional[np.ndarray] = None
+        self.iterations_run = 0
+
+    def _trained(self) -> bool:
+        return self.weights is not None
+
+    def trainFeatures(self, X, y) -> None:
+        """train() on feature rows that exist already (host arrays or device tensors, as
+        OffLineDataProvider.split returns them).  :85-114 -- the config_* keys select the static
+        train(...) (regParam 0.0), otherwise the default LogisticRegressionWithSGD().run
+        (regParam 0.01)."""
+        c = self.config
+        if all(k in c for k in ("config_num_iterations", "config_step_size",
+                                "config_mini_batch_fraction")):
+            self.weights, self.iterations_run = sgd_train(
+                self.context, X, y, num_iterations=int(c["config_num_iterations"]),
+                step_size=float(c["config_step_size"]), reg_param=0.0,
+                mini_batch_fraction=float(c["config_mini_batch_fraction"]),
+                num_partitions=self.num_partitions)
+        else:
+            self.weights, self.iterations_run = sgd_train(
+                self.context, X, y, DEFAULT_NUM_ITERATIONS, DEFAULT_STEP_SIZE, DEFAULT_REG_PARAM,
+                DEFAULT_MINI_BATCH_FRACTION)
+
+    def _predict_rows(self, features):
+        return predict(self.context, features, self.weights)
+
+
+class SVMClassifier(LogisticRegressionClassifier):
+    """IClassifier for train_clf=svm (SVMClassifier.java), GPU-resident: the same flow and model
+    attributes as LogisticRegressionClassifier with SVMWithSGD and SVMModel.predict."""
+
+    def trainFeatures(self, X, y) -> None:
         """:83-111 -- with config_num_iterations / config_step_size / config_reg_param /
         config_mini_batch_fraction all set, the static SVMWithSGD.train(rdd, iterations, step,
         regParam, fraction); otherwise new SVMWithSGD().run (step 1.0, 100 iterations,
         regParam 0.01, fraction 1.0)."""
-        self.fe = fe
-        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
-
-    def trainFeatures(self, X, y) -> None:
         c = self.config
         if all(k in c for k in ("config_num_iterations", "config_step_size", "config_reg_param",
                                 "config_mini_batch_fraction")):
@@ -445,9 +444,7 @@ class SVMClassifier(LogisticRegressionClassifier):
                 self.context, X, y, DEFAULT_NUM_ITERATIONS, DEFAULT_STEP_SIZE, DEFAULT_REG_PARAM,
                 DEFAULT_MINI_BATCH_FRACTION)
 
-    def predict(self, features) -> np.ndarray:
-        if self.weights is None:
-            raise RuntimeError("The classifier has not been trained")  # IllegalStateException
+    def _predict_rows(self, features):
         return svm_predict(self.context, features, self.weights)
 
 
@@ -459,7 +456,7 @@ def _tree_config(c: Dict[str, str]) -> dict:
                 min_instances_per_node=int(c["config_min_instances_per_node"]))
 
 
-class DecisionTreeClassifier(LogisticRegressionClassifier):
+class DecisionTreeClassifier(_Classifier):
     """IClassifier for train_clf=dt (DecisionTreeClassifier.java), GPU-resident: the flow of
     LogisticRegressionClassifier with MLlib's DecisionTree and DecisionTreeModel.predict."""
 
@@ -472,29 +469,20 @@ class DecisionTreeClassifier(LogisticRegressionClassifier):
         # seed of the threshold sample of more than max(max_bins^2, 10000) rows
         self.split_seed = 0
 
-    def train(self, epochs, targets: Sequence[float], fe) -> None:
+    def _trained(self) -> bool:
+        return self.nodes is not None
+
+    def trainFeatures(self, X, y) -> None:
         """:85-127 -- Strategy.defaultStrategy("Classification") (Gini, depth 5, 32 bins, 1
         instance per node); with config_max_bins / config_impurity / config_max_depth /
         config_min_instances_per_node all set, those instead ("gini" is Gini, any other string
         Entropy)."""
-        self.fe = fe
-        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
-
-    def trainFeatures(self, X, y) -> None:
         c = self.config
         kw = _tree_config(c) if all(k in c for k in self.CONFIG_KEYS) else {}
         self.nodes = dtree_train(self.context, X, y, split_seed=self.split_seed, **kw)
 
-    def predict(self, features) -> np.ndarray:
-        if self.nodes is None:
-            raise RuntimeError("The classifier has not been trained")  # IllegalStateException
+    def _predict_rows(self, features):
         return dtree_predict(self.context, features, self.nodes)
-
-    def test(self, epochs, targets: Sequence[float]) -> ClassificationStatistics:
-        if self.nodes is None:
-            raise RuntimeError("The classifier has not been trained")
-        pred = self.predict(self._features(epochs))
-        return reference_statistics(pred, targets)
 
 
 class RandomForestClassifier(DecisionTreeClassifier):
@@ -508,14 +496,10 @@ class RandomForestClassifier(DecisionTreeClassifier):
         super().__init__(context)
         self.tree_offsets: Optional[np.ndarray] = None
 
-    def train(self, epochs, targets: Sequence[float], fe) -> None:
+    def trainFeatures(self, X, y) -> None:
         """:101-136 -- Strategy.defaultStrategy("Classification"), 100 trees, "auto", seed 12345;
         with all six config keys set, their values instead ("gini" is Gini, any other string
         Entropy; a feature subset that is no strategy's name is Spark's failed require)."""
-        self.fe = fe
-        self.trainFeatures(self._features(epochs), np.asarray(targets, dtype=np.float64))
-
-    def trainFeatures(self, X, y) -> None:
         c = self.config
         kw = {}
         if all(k in c for k in self.CONFIG_KEYS):
@@ -528,9 +512,7 @@ class RandomForestClassifier(DecisionTreeClassifier):
             self.context, X, y, num_partitions=self.num_partitions, split_seed=self.split_seed,
             **kw)
 
-    def predict(self, features) -> np.ndarray:
-        if self.nodes is None:
-            raise RuntimeError("The classifier has not been trained")  # IllegalStateException
+    def _predict_rows(self, features):
         return rforest_predict(self.context, features, self.nodes, self.tree_offsets)
 
 

@@ -84,26 +84,6 @@ constexpr size_t kZeroCopyBytes = (size_t)768 << 10;
 constexpr size_t kZeroCopyOutBytes =
     kZeroCopyBytes / (sizeof(double) * EEGFX_DWT8_EPOCH_SIZE) * EEGFX_DWT8_FEATURE_SIZE * sizeof(double);
 
-void* stage_in(eegfx_ctx* ctx, DevBuf& buf, const void* src, size_t bytes, int mem) {
-  if (mem == EEGFX_MEM_DEVICE) return const_cast<void*>(src);
-  void* d = buf.get(bytes);
-  if (bytes) HIP_CHECK(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return d;
-}
-
-// Where a call's results are written on the device: the caller's buffer, or the context's.
-template <typename T>
-T* dev_out(DevBuf& buf, T* caller, size_t bytes, int mem) {
-  return mem == EEGFX_MEM_DEVICE ? caller : (T*)buf.get(bytes);
-}
-
-// A call's results back to a host caller, and the stream drained; nothing for a device caller.
-void copy_out(eegfx_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes, int mem) {
-  if (mem != EEGFX_MEM_HOST) return;
-  HIP_CHECK(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  ctx->drain();
-}
-
 // The front door of the raw-recording entries.  The order of the checks is part of the interface
 // (tests/test_gpu_api_errors.py): null context, mem flag, format, sizes, null buffers
 // (check_raw_head), then the channel selection: C, null cols / res, each column.  `out`: the
@@ -129,7 +109,7 @@ bool stage_raw(eegfx_ctx* ctx, const void* raw, const int64_t* pos, int64_t n, i
   ctx->activate();
   const size_t raw_bytes = (size_t)n_frames * ct * (fmt == EEGFX_INT_16 ? 2 : 4);
   in->raw = stage_in(ctx, ctx->raw, raw, raw_bytes, mem);
-  in->pos = (const int64_t*)stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
+  in->pos = stage_in(ctx, ctx->pos, pos, sizeof(int64_t) * n, mem);
   return true;
 }
 
@@ -268,8 +248,7 @@ int process_recording_epochs_api(eegfx_ctx* ctx, const void* raw, int32_t fmt, i
     E* d_ep = dev_out(ctx->scratch, epochs_out, ep_bytes, mem);
     double* d_f = dev_out(ctx->out, features, f_bytes, mem);
     run_epochs_and_features(ctx, in.raw, fmt, n_frames, ct, sel, C, in.pos, n, d_ep, d_f);
-    if (mem == EEGFX_MEM_HOST)  // both copies ahead of copy_out's one drain
-      HIP_CHECK(hipMemcpyAsync(epochs_out, d_ep, ep_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    copy_back(ctx, epochs_out, d_ep, ep_bytes, mem);  // both copies ahead of copy_out's one drain
     copy_out(ctx, features, d_f, f_bytes, mem);
   });
 }
@@ -573,29 +552,20 @@ int eegfx_plan_markers_device(eegfx_ctx* ctx, const int64_t* positions,
     if (!positions || !stimulus_index) fail(EEGFX_EINVAL, "null markers");
     ctx->activate();
     const int64_t n = n_markers;
-    const int64_t* d_pos = (const int64_t*)stage_in(ctx, ctx->pos, positions, sizeof(int64_t) * n,
-                                                    mem);
-    const int32_t* d_stim = (const int32_t*)stage_in(ctx, ctx->lr_y, stimulus_index,
-                                                     sizeof(int32_t) * n, mem);
-    int64_t* d_pos_out = pos_out;
-    double* d_label = label_out;
-    if (mem == EEGFX_MEM_HOST) {
-      uint8_t* o = (uint8_t*)ctx->out.get((sizeof(int64_t) + sizeof(double)) * (size_t)n);
-      d_pos_out = pos_out ? (int64_t*)o : nullptr;
-      d_label = label_out ? (double*)(o + sizeof(int64_t) * (size_t)n) : nullptr;
-    }
+    const int64_t* d_pos = stage_in(ctx, ctx->pos, positions, sizeof(int64_t) * n, mem);
+    const int32_t* d_stim = stage_in(ctx, ctx->row_vals, stimulus_index, sizeof(int32_t) * n, mem);
+    // a host caller's two outputs share one allocation, pos_out[n] then label_out[n]; null for a
+    // device caller, whose buffers are written in place
+    uint8_t* o = dev_out<uint8_t>(ctx->out, nullptr, (sizeof(int64_t) + sizeof(double)) * (size_t)n,
+                                  mem);
+    int64_t* d_pos_out = o && pos_out ? (int64_t*)o : pos_out;
+    double* d_label = o && label_out ? (double*)(o + sizeof(int64_t) * (size_t)n) : label_out;
     void* scratch = ctx->scratch.get(plan_scratch_bytes(n));
     PlanResult r;
     HIP_CHECK(launch_plan_markers(ctx->stream, d_pos, d_stim, n, n_frames, guessed,
                                   (int)*balance, scratch, d_pos_out, d_label, &r));
-    if (mem == EEGFX_MEM_HOST && r.selected > 0) {
-      if (pos_out)
-        HIP_CHECK(hipMemcpyAsync(pos_out, d_pos_out, sizeof(int64_t) * (size_t)r.selected,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-      if (label_out)
-        HIP_CHECK(hipMemcpyAsync(label_out, d_label, sizeof(double) * (size_t)r.selected,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (pos_out) copy_back(ctx, pos_out, d_pos_out, sizeof(int64_t) * (size_t)r.selected, mem);
+    if (label_out) copy_back(ctx, label_out, d_label, sizeof(double) * (size_t)r.selected, mem);
     ctx->drain();
     *balance = r.balance;
     *n_selected = r.selected;

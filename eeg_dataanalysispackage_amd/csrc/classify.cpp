@@ -59,7 +59,7 @@ static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double
     check_mem(mem);
     if (n < 1) fail(EEGFX_EINVAL, "empty training set");  // GeneralizedLinearAlgorithm: first()
     if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
-    if (d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "d=%d outside [1, %d]", d, kLrMaxFeatures);
+    check_train_d(d);
     if (num_iterations < 0) fail(EEGFX_EINVAL, "num_iterations %d", num_iterations);
     // RDD.sample's require(fraction >= 0.0), then BernoulliSampler's upper bound 1 up to
     // RandomSampler.roundingEpsilon
@@ -73,18 +73,7 @@ static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double
            mini_batch_fraction);
     if (sampled && num_partitions < 1) fail(EEGFX_EINVAL, "num_partitions %d", num_partitions);
     ctx->activate();
-    const double* dX = X;
-    const double* dy = y;
-    if (mem == EEGFX_MEM_HOST) {
-      double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
-      double* by = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
-      HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice,
-                               ctx->stream));
-      HIP_CHECK(hipMemcpyAsync(by, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice,
-                               ctx->stream));
-      dX = bx;
-      dy = by;
-    }
+    const auto [dX, dy] = stage_xy(ctx, X, y, n, d, mem);
     const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
     std::vector<uint8_t> hs(sbytes, 0);
     LrState* h = (LrState*)hs.data();
@@ -139,7 +128,7 @@ static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double
     }
     HIP_CHECK(hipMemcpyAsync(hs.data(), st, sbytes, hipMemcpyDeviceToHost, ctx->stream));
     ctx->drain();
-    if (h->converged == 2) fail(EEGFX_EINVAL, "Input validation failed: labels must be 0.0 or 1.0");
+    if (h->converged == 2) fail(EEGFX_EINVAL, "%s", kBadLabels);
     memcpy(weights, h->w, sizeof(double) * (size_t)d);
     if (iterations_run) *iterations_run = h->iter;
   });
@@ -151,30 +140,18 @@ static int glm_predict(int grad, eegfx_ctx* ctx, const double* X, int64_t n, int
   return guarded([&] {
     if (!ctx || !weights) fail(EEGFX_EINVAL, "null argument");
     check_mem(mem);
-    if (n < 0 || d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "n=%lld d=%d", (long long)n, d);
+    check_predict_dims(n, d);
     if (n == 0) return;
     if (!X || !out) fail(EEGFX_EINVAL, "null X / out");
-    ctx->activate();
-    const double* dX = X;
-    double* dout = out;
-    if (mem == EEGFX_MEM_HOST) {
-      double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
-      HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice,
+    predict_frame(ctx, X, n, d, out, mem, [&](const double* dX, double* dout) {
+      const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
+      LrState* st = (LrState*)ctx->lr_state.get(sbytes);
+      HIP_CHECK(hipMemcpyAsync(st->w, weights, sizeof(double) * (size_t)d, hipMemcpyHostToDevice,
                                ctx->stream));
-      dX = bx;
-      dout = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
-    }
-    const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
-    LrState* st = (LrState*)ctx->lr_state.get(sbytes);
-    HIP_CHECK(hipMemcpyAsync(st->w, weights, sizeof(double) * (size_t)d, hipMemcpyHostToDevice,
-                             ctx->stream));
-    const bool use_t = !std::isnan(threshold);  // clearThreshold -> scores / margins
-    HIP_CHECK(launch_lr_predict(ctx->stream, grad, dX, n, d, st->w, intercept, threshold,
-                                use_t ? 1 : 0, dout));
-    if (mem == EEGFX_MEM_HOST)
-      HIP_CHECK(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost,
-                               ctx->stream));
-    ctx->drain();
+      const bool use_t = !std::isnan(threshold);  // clearThreshold -> scores / margins
+      HIP_CHECK(launch_lr_predict(ctx->stream, grad, dX, n, d, st->w, intercept, threshold,
+                                  use_t ? 1 : 0, dout));
+    });
   });
 }
 

@@ -1,13 +1,15 @@
 // ctx.h -- the device context (struct eegfx_ctx) and the helpers that the host sources share:
+// the staging of host-memory arguments (stage_in, dev_out, copy_out and what is built on them),
 // the argument checks (defined in api.cpp) and the device-pointer pipelines (routes.cpp), used by
-// api.cpp, streamed.cpp, classify.cpp, mailbox.cpp, flow.cpp and odp.cpp (the
-// OffLineDataProvider).
+// api.cpp, routes.cpp, streamed.cpp, classify.cpp, tree_driver.cpp, mailbox.cpp, flow.cpp and
+// odp.cpp (the OffLineDataProvider).
 // Internal: not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdint>
 #include <map>
@@ -165,16 +167,33 @@ struct eegfx_ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   std::vector<int64_t> event_bytes;
   size_t n_timed = 0;
+  // The grow-only device buffers.  A call drains the stream before it returns, so entries share
+  // them freely from call to call; two buffers that one call uses at once stay apart.  Each is
+  // also named in buffers() below -- the one other place a new buffer is added.
+  // The raw entries (api.cpp, streamed.cpp, odp.cpp) and eegfx_plan_markers_device: a host
+  // caller's recording and positions, the results on their way back (plan: pos_out ++ label_out),
+  // the intermediate epochs / window chunks / plan scratch, the fused kernels' scratch.
   DevBuf raw, pos, out, scratch, fused;
-  DevBuf lr_x, lr_y, lr_state, lr_part, lr_mask;  // logistic regression (eegfx_logreg_*)
-  // the decision tree (eegfx_dtree_*): threshold table, bins, slot + label per row, one group's
-  // histograms (and the gathered split sample), a level's decisions / the nodes of a prediction
-  DevBuf dt_tab, dt_bins, dt_rows, dt_hist, dt_dec;
-  // the random forest (eegfx_rforest_*) on top of them: weight per tree and row, slot per tree and
-  // row, a group's feature subsets and launch tree lists / the tree offsets of a prediction
+  // Host callers' rows, shared by eegfx_logreg_* / eegfx_svm_* / eegfx_dtree_* / eegfx_rforest_*
+  // train and predict (stage_xy, predict_frame): X [n][d] in; one value per row -- the labels in
+  // (train) or the predictions out (predict), and the int32 stimulus index per marker of
+  // eegfx_plan_markers_device.
+  DevBuf rows_x, row_vals;
+  // eegfx_logreg_* / eegfx_svm_*: LrState (train: state and weights; predict: the weights), the
+  // gradient partials, a chunk of mini-batch masks
+  DevBuf lr_state, lr_part, lr_mask;
+  // eegfx_dtree_train / eegfx_rforest_train (dt_bin_rows, grow_trees): threshold table, bins, slot
+  // + label per row, one group's histograms (and the gathered split sample).  dt_nodes: records
+  // per node from the host -- a group's DtDecisions (train), the model's DtNodes
+  // (eegfx_dtree_predict / eegfx_rforest_predict).
+  DevBuf dt_tab, dt_bins, dt_rows, dt_hist, dt_nodes;
+  // the bagged or subsampled forest on top of them: weight per tree and row, slot per tree and
+  // row.  rf_tab: int32 tables from the host -- a group's feature subsets and launch tree lists
+  // (eegfx_rforest_train), the tree offsets (eegfx_rforest_predict).
   DevBuf rf_weight, rf_slot, rf_tab;
-  // the train/test flow (flow.cpp, eegfx_odp_split): rows to gather from / predictions, the
-  // indices, the gathered rows, labels in, labels out, and the kernels' flag / counter block
+  // the train/test flow: rows to gather from (eegfx_gather_rows, eegfx_odp_split) / predictions
+  // (eegfx_confusion_counts); the indices, the gathered rows (gather, split); labels in (split,
+  // confusion); labels out (split); the kernels' flag / counter block (all three).
   DevBuf fl_src, fl_idx, fl_dst, fl_lab, fl_y, fl_flag;
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
   PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
@@ -202,19 +221,18 @@ struct eegfx_ctx {
     return Guard{guard_dev, (int64_t*)guard_list.get(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1)),
                  guard_recomputed_slots(), guard_rechecked_slots(), guard_adapt(), track_dev()};
   }
-  void bind_buffers() {
-    for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec,
+  // every DevBuf of the context: bound to the stream at creation, released at destruction
+  auto buffers() {
+    return std::array{&raw, &pos, &out, &scratch, &fused, &rows_x, &row_vals, &lr_state, &lr_part,
+                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_nodes,
                       &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
-                      &fl_flag})
-      b->sp = &stream;
+                      &fl_flag};
+  }
+  void bind_buffers() {
+    for (DevBuf* b : buffers()) b->sp = &stream;
   }
   void release_buffers() {
-    for (DevBuf* b : {&raw, &pos, &out, &scratch, &fused, &lr_x, &lr_y, &lr_state, &lr_part,
-                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_dec,
-                      &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
-                      &fl_flag})
-      b->release();
+    for (DevBuf* b : buffers()) b->release();
     pin_in.release();
     pin_out.release();
     pin_chunk[0].release();
@@ -332,6 +350,67 @@ struct eegfx_ctx {
 namespace eegfx {
 
 void check_mem(int mem);
+
+// ---- a `mem` argument becomes device pointers.  Everything is queued on the context stream.
+// An argument as the kernels read it: the caller's device pointer, or a copy of the host array in
+// `buf` (T const for an input; not for an output whose first contents count).
+template <typename T>
+T* stage_in(eegfx_ctx* ctx, DevBuf& buf, T* src, size_t bytes, int mem) {
+  if (mem == EEGFX_MEM_DEVICE) return src;
+  void* d = buf.get(bytes);
+  if (bytes) HIP_CHECK(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return (T*)d;
+}
+// Where a call's results are written on the device: the caller's buffer, or the context's.
+template <typename T>
+T* dev_out(DevBuf& buf, T* caller, size_t bytes, int mem) {
+  return mem == EEGFX_MEM_DEVICE ? caller : (T*)buf.get(bytes);
+}
+// A call's results queued back to a host caller; nothing for a device caller or for no bytes.
+// No drain: the classifier, tree, gather and confusion entries drain for both memory kinds.
+inline void copy_back(eegfx_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes, int mem) {
+  if (mem == EEGFX_MEM_HOST && bytes)
+    HIP_CHECK(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+}
+// ... and the stream drained for that host caller (the raw entries: a device caller's results
+// stay stream-ordered).
+inline void copy_out(eegfx_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes, int mem) {
+  copy_back(ctx, host_dst, dev_src, bytes, mem);
+  if (mem == EEGFX_MEM_HOST) ctx->drain();
+}
+
+// ---- the classifier entries' front door and frames
+constexpr const char* kBadLabels = "Input validation failed: labels must be 0.0 or 1.0";
+inline void check_train_d(int32_t d) {
+  if (d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "d=%d outside [1, %d]", d, kLrMaxFeatures);
+}
+inline void check_predict_dims(int64_t n, int32_t d) {
+  if (n < 0 || d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "n=%lld d=%d", (long long)n, d);
+}
+// The training pair of glm_sgd_train and dt_bin_rows as the kernels read it.
+struct TrainXY {
+  const double* X;
+  const double* y;
+};
+inline TrainXY stage_xy(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                        int mem) {
+  const double* dX = stage_in(ctx, ctx->rows_x, X, sizeof(double) * (size_t)(n * d), mem);
+  return {dX, stage_in(ctx, ctx->row_vals, y, sizeof(double) * (size_t)n, mem)};
+}
+// The frame of a predict call (glm_predict, predict_rows; n > 0): X staged, launch(dX, dout)
+// uploads the model and runs the kernel, the predictions go back to a host caller, and the stream
+// drains for both memory kinds -- the model is read out of the caller's arrays until then.
+template <typename Launch>
+void predict_frame(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d, double* out, int mem,
+                   Launch&& launch) {
+  ctx->activate();
+  const double* dX = stage_in(ctx, ctx->rows_x, X, sizeof(double) * (size_t)(n * d), mem);
+  double* dout = dev_out(ctx->row_vals, out, sizeof(double) * (size_t)n, mem);
+  launch(dX, dout);
+  copy_back(ctx, out, dout, sizeof(double) * (size_t)n, mem);
+  ctx->drain();
+}
+
 // The processors this process may run on (classify.cpp): Spark local[*]'s defaultParallelism.
 int available_processors();
 // tree_driver.cpp: the binned rows of a tree or forest call.  Host: the threshold table `tab`

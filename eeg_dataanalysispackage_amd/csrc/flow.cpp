@@ -88,26 +88,13 @@ int eegfx_gather_rows(eegfx_ctx* ctx, const double* src, int64_t n_src, int32_t 
     if (!idx || !dst || (n_src > 0 && !src)) fail(EEGFX_EINVAL, "null src / idx / dst");
     ctx->activate();
     const size_t row = sizeof(double) * (size_t)d;
-    const double* d_src = src;
-    const int64_t* d_idx = idx;
-    double* d_dst = dst;
-    if (mem == EEGFX_MEM_HOST) {
-      double* bs = (double*)ctx->fl_src.get(row * (size_t)n_src);
-      int64_t* bi = (int64_t*)ctx->fl_idx.get(sizeof(int64_t) * (size_t)m);
-      d_dst = (double*)ctx->fl_dst.get(row * (size_t)m);
-      if (n_src)
-        HIP_CHECK(hipMemcpyAsync(bs, src, row * (size_t)n_src, hipMemcpyHostToDevice, ctx->stream));
-      HIP_CHECK(hipMemcpyAsync(bi, idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice,
-                               ctx->stream));
-      // the rows of bad indices keep what the caller's buffer holds
-      HIP_CHECK(hipMemcpyAsync(d_dst, dst, row * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-      d_src = bs;
-      d_idx = bi;
-    }
+    const double* d_src = stage_in(ctx, ctx->fl_src, src, row * (size_t)n_src, mem);
+    const int64_t* d_idx = stage_in(ctx, ctx->fl_idx, idx, sizeof(int64_t) * (size_t)m, mem);
+    // dst goes up too: the rows of bad indices keep what the caller's buffer holds
+    double* d_dst = stage_in(ctx, ctx->fl_dst, dst, row * (size_t)m, mem);
     run_gather_rows(ctx, d_src, n_src, d, d_idx, m, d_dst, 0);
-    if (mem == EEGFX_MEM_HOST)
-      HIP_CHECK(hipMemcpyAsync(dst, d_dst, row * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    gather_check(ctx, 1, n_src);
+    copy_back(ctx, dst, d_dst, row * (size_t)m, mem);
+    gather_check(ctx, 1, n_src);  // drains for both memory kinds
   });
 }
 
@@ -122,18 +109,9 @@ int eegfx_confusion_counts(eegfx_ctx* ctx, const double* pred, const double* lab
     memset(&h, 0, sizeof(h));
     if (n > 0) {
       ctx->activate();
-      const double* d_pred = pred;
-      const double* d_lab = labels;
-      if (mem == EEGFX_MEM_HOST) {
-        double* bp = (double*)ctx->fl_src.get(sizeof(double) * (size_t)n);
-        double* bl = (double*)ctx->fl_lab.get(sizeof(double) * (size_t)n);
-        HIP_CHECK(hipMemcpyAsync(bp, pred, sizeof(double) * (size_t)n, hipMemcpyHostToDevice,
-                                 ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(bl, labels, sizeof(double) * (size_t)n, hipMemcpyHostToDevice,
-                                 ctx->stream));
-        d_pred = bp;
-        d_lab = bl;
-      }
+      const size_t bytes = sizeof(double) * (size_t)n;
+      const double* d_pred = stage_in(ctx, ctx->fl_src, pred, bytes, mem);
+      const double* d_lab = stage_in(ctx, ctx->fl_lab, labels, bytes, mem);
       ConfusionOut* out =
           (ConfusionOut*)((unsigned long long*)ctx->fl_flag.get(kFlagBytes) + 2);
       HIP_CHECK(hipMemsetAsync(out, 0, sizeof(*out), ctx->stream));
@@ -141,8 +119,7 @@ int eegfx_confusion_counts(eegfx_ctx* ctx, const double* pred, const double* lab
       HIP_CHECK(hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
       ctx->drain();
     }
-    if (h.seen & kSeenOther)
-      fail(EEGFX_EINVAL, "Input validation failed: labels must be 0.0 or 1.0");
+    if (h.seen & kSeenOther) fail(EEGFX_EINVAL, "%s", kBadLabels);
     // MulticlassMetrics' matrix has one row per actual class: with fewer than two the
     // reference's cm[1] throws (LogisticRegressionClassifier.java:131)
     if (h.seen != (kSeenZero | kSeenOne))

@@ -586,12 +586,8 @@ int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_f
     char* rows = (char*)ctx->fl_src.get(row * (size_t)n);
     int64_t* d_perm = (int64_t*)ctx->fl_idx.get(sizeof(int64_t) * (size_t)n);
     double* d_lab = (double*)ctx->fl_lab.get(sizeof(double) * (size_t)n);
-    double* d_X = X;
-    double* d_y = y;
-    if (mem == EEGFX_MEM_HOST) {
-      d_X = (double*)ctx->fl_dst.get(row * (size_t)n);
-      d_y = (double*)ctx->fl_y.get(sizeof(double) * (size_t)n);
-    }
+    double* d_X = dev_out(ctx->fl_dst, X, row * (size_t)n, mem);
+    double* d_y = dev_out(ctx->fl_y, y, sizeof(double) * (size_t)n, mem);
     ctx->drain();
     odp->feature_rows(skip, feature_size, [&](eegfx_ctx* c, const eegfx_odp::Shard& s,
                                               const double* from, size_t bytes) {
@@ -608,12 +604,9 @@ int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_f
                              hipMemcpyHostToDevice, ctx->stream));
     run_gather_rows(ctx, (const double*)rows, n, d, d_perm, n, d_X, 0);
     run_gather_rows(ctx, d_lab, n, 1, d_perm, n, d_y, 1);
-    if (mem == EEGFX_MEM_HOST) {
-      HIP_CHECK(hipMemcpyAsync(X, d_X, row * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(hipMemcpyAsync(y, d_y, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost,
-                               ctx->stream));
-    }
-    gather_check(ctx, 2, n);
+    copy_back(ctx, X, d_X, row * (size_t)n, mem);
+    copy_back(ctx, y, d_y, sizeof(double) * (size_t)n, mem);
+    gather_check(ctx, 2, n);  // drains for both memory kinds
   });
 }
 

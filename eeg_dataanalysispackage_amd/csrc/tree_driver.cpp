@@ -38,16 +38,7 @@ void eegfx::dt_bin_rows(eegfx_ctx* ctx, const double* X, const double* y, int64_
   const int64_t m = rows.empty() && n <= required ? n : (int64_t)rows.size();
   if (m < 1) fail(EEGFX_EINVAL, "the split sample is empty");
 
-  const double* dX = X;
-  const double* dy = y;
-  if (mem == EEGFX_MEM_HOST) {
-    double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
-    double* by = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
-    HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(by, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    dX = bx;
-    dy = by;
-  }
+  const auto [dX, dy] = stage_xy(ctx, X, y, n, d, mem);
   // one allocation for the sample (device X only) and the histograms of a group after it
   const size_t sample_bytes = mem == EEGFX_MEM_DEVICE ? sizeof(double) * (size_t)(m * d) : 0;
   const size_t idx_bytes = sizeof(int64_t) * rows.size();
@@ -83,8 +74,7 @@ void eegfx::dt_bin_rows(eegfx_ctx* ctx, const double* X, const double* y, int64_
     }
     // one sort per feature, threads over the features (the sorts are
     // most of a call's time on one thread)
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int W = (int)std::min({(unsigned)d, 8u, hw});
+    const int W = std::min({(int)d, 8, available_processors()});
     std::vector<char> failed((size_t)W, 0);  // no exception leaves a thread
     {
       Joiner pool;
@@ -128,7 +118,7 @@ void check_tree_params(const eegfx_ctx* ctx, int mem, int64_t n, int32_t d, int3
   check_mem(mem);
   // n == 1: numBins = 1 leaves no split, and Spark's assertion fails
   if (n < 2 || n > INT32_MAX) fail(EEGFX_EINVAL, "n=%lld outside [2, 2^31)", (long long)n);
-  if (d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "d=%d outside [1, %d]", d, kLrMaxFeatures);
+  check_train_d(d);
   if (capacity < 0) fail(EEGFX_EINVAL, "capacity %d", capacity);
   if (null_arg) fail(EEGFX_EINVAL, "null argument");
   if (impurity != EEGFX_GINI && impurity != EEGFX_ENTROPY)
@@ -273,7 +263,7 @@ Forest grow_trees(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, i
       if (first) {  // the first synchronisation reads dt_bin_kernel's flags
         const int32_t* flags = (const int32_t*)binned.tab.data();
         if (flags[0]) fail(EEGFX_EINVAL, "a training feature is not finite");
-        if (flags[1]) fail(EEGFX_EINVAL, "Input validation failed: labels must be 0.0 or 1.0");
+        if (flags[1]) fail(EEGFX_EINVAL, "%s", kBadLabels);
         first = false;
       }
       for (int i = c0; i < c0 + cn; ++i) {
@@ -300,7 +290,7 @@ Forest grow_trees(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, i
       dec[i].left = child_seq[2 * (size_t)i];
       dec[i].right = child_seq[2 * (size_t)i + 1];
     }
-    DtDecision* ddec = (DtDecision*)ctx->dt_dec.get(sizeof(DtDecision) * dec.size());
+    DtDecision* ddec = (DtDecision*)ctx->dt_nodes.get(sizeof(DtDecision) * dec.size());
     HIP_CHECK(hipMemcpyAsync(ddec, dec.data(), sizeof(DtDecision) * dec.size(),
                              hipMemcpyHostToDevice, st));
     HIP_CHECK(launch_rf_route(st, binned.bins, n, d, dtab + group_trees_at, group_nt, s0, gn,
@@ -312,39 +302,29 @@ Forest grow_trees(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, i
   return out;
 }
 
-// The back half of both predict entries, after their checks: X and the output staged on the device
-// (host memory) or used in place, the nodes uploaded as DtNode, one walk kernel, the copy back.
+// The back half of both predict entries, after their checks: inside the predict frame, the nodes
+// uploaded as DtNode and one walk kernel.
 // tree_offsets: num_trees + 1 offsets into `nodes` and the vote over the trees; nullptr: one tree.
 void predict_rows(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
                   const eegfx_tree_node* nodes, int32_t n_nodes, const int32_t* tree_offsets,
                   int32_t num_trees, double* out, int mem) {
-  ctx->activate();
-  const hipStream_t st = ctx->stream;
-  const double* dX = X;
-  double* dout = out;
-  if (mem == EEGFX_MEM_HOST) {
-    double* bx = (double*)ctx->lr_x.get(sizeof(double) * (size_t)(n * d));
-    HIP_CHECK(hipMemcpyAsync(bx, X, sizeof(double) * (size_t)(n * d), hipMemcpyHostToDevice, st));
-    dX = bx;
-    dout = (double*)ctx->lr_y.get(sizeof(double) * (size_t)n);
-  }
-  std::vector<DtNode> hn((size_t)n_nodes);
+  std::vector<DtNode> hn((size_t)n_nodes);  // outlives the frame's drain
   for (int32_t i = 0; i < n_nodes; ++i)
     hn[i] = DtNode{nodes[i].feature, nodes[i].left, nodes[i].right, 0, nodes[i].threshold,
                    nodes[i].predict};
-  DtNode* dn = (DtNode*)ctx->dt_dec.get(sizeof(DtNode) * hn.size());
-  HIP_CHECK(hipMemcpyAsync(dn, hn.data(), sizeof(DtNode) * hn.size(), hipMemcpyHostToDevice, st));
-  if (tree_offsets) {
-    int32_t* doff = (int32_t*)ctx->rf_tab.get(sizeof(int32_t) * ((size_t)num_trees + 1));
-    HIP_CHECK(hipMemcpyAsync(doff, tree_offsets, sizeof(int32_t) * ((size_t)num_trees + 1),
-                             hipMemcpyHostToDevice, st));
-    HIP_CHECK(launch_rf_predict(st, dX, n, d, dn, doff, num_trees, dout));
-  } else {
-    HIP_CHECK(launch_dt_predict(st, dX, n, d, dn, n_nodes, dout));
-  }
-  if (mem == EEGFX_MEM_HOST)
-    HIP_CHECK(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-  ctx->drain();
+  predict_frame(ctx, X, n, d, out, mem, [&](const double* dX, double* dout) {
+    const hipStream_t st = ctx->stream;
+    DtNode* dn = (DtNode*)ctx->dt_nodes.get(sizeof(DtNode) * hn.size());
+    HIP_CHECK(hipMemcpyAsync(dn, hn.data(), sizeof(DtNode) * hn.size(), hipMemcpyHostToDevice, st));
+    if (tree_offsets) {
+      int32_t* doff = (int32_t*)ctx->rf_tab.get(sizeof(int32_t) * ((size_t)num_trees + 1));
+      HIP_CHECK(hipMemcpyAsync(doff, tree_offsets, sizeof(int32_t) * ((size_t)num_trees + 1),
+                               hipMemcpyHostToDevice, st));
+      HIP_CHECK(launch_rf_predict(st, dX, n, d, dn, doff, num_trees, dout));
+    } else {
+      HIP_CHECK(launch_dt_predict(st, dX, n, d, dn, n_nodes, dout));
+    }
+  });
 }
 
 }  // namespace
@@ -375,7 +355,7 @@ int eegfx_dtree_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
   return guarded([&] {
     if (!ctx) fail(EEGFX_EINVAL, "null context");
     check_mem(mem);
-    if (n < 0 || d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "n=%lld d=%d", (long long)n, d);
+    check_predict_dims(n, d);
     if (n_nodes < 1) fail(EEGFX_EINVAL, "n_nodes %d", n_nodes);
     if (!nodes || (n > 0 && (!X || !out))) fail(EEGFX_EINVAL, "null argument");
     if (!dtree::nodes_valid(nodes, n_nodes, d))
@@ -423,7 +403,7 @@ int eegfx_rforest_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
   return guarded([&] {
     if (!ctx) fail(EEGFX_EINVAL, "null context");
     check_mem(mem);
-    if (n < 0 || d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "n=%lld d=%d", (long long)n, d);
+    check_predict_dims(n, d);
     if (num_trees < 1) fail(EEGFX_EINVAL, "num_trees %d", num_trees);
     if (!nodes || !tree_offsets || (n > 0 && (!X || !out))) fail(EEGFX_EINVAL, "null argument");
     if (!rforest::forest_valid(nodes, tree_offsets, num_trees, d))

@@ -53,6 +53,32 @@ def test_reference_statistics_mapping():
         ref.reference_statistics([0, 1, 1], [0, 0, 0])
 
 
+def test_classifier_base_guards_without_a_device():
+    """What the four IClassifiers inherit, with no device used: the untrained guard of predict /
+    test / testFeatures, train's need of a feature extraction, and setConfig's copy."""
+    import numpy as np
+    import pytest
+    from eeg_dataanalysispackage_amd import classification as clf
+    for cls in (clf.LogisticRegressionClassifier, clf.SVMClassifier, clf.DecisionTreeClassifier,
+                clf.RandomForestClassifier):
+        c = cls()
+        rows, labels = np.zeros((2, 3)), [0.0, 1.0]
+        for call in (lambda: c.predict(rows), lambda: c.test(rows, labels),
+                     lambda: c.testFeatures(rows, labels)):
+            with pytest.raises(RuntimeError) as e:
+                call()
+            assert str(e.value) == "The classifier has not been trained"
+        with pytest.raises(ValueError) as e:
+            c.train(rows, labels, None)
+        assert str(e.value) == "no feature extraction set"
+        assert c.getFeatureExtraction() is None
+        config = {"config_max_depth": "3"}
+        c.setConfig(config)
+        config["config_max_depth"] = "4"
+        assert c.config == {"config_max_depth": "3"} and c.config is not config
+        assert c._ctx is None  # no context was created on the way
+
+
 def test_mllib_restatement_basics():
     import numpy as np
     from oracle import mllib_logreg as ref
