@@ -1,9 +1,14 @@
 """Device marker planning (scan over 3-state balance maps) against the sequential host planner,
 which is pinned to the reference goldens (OfflineDataProviderTest / Epochs.csv selections)."""
+from ctypes import byref, c_int64
+
 import numpy as np
 import pytest
 
 import eeg_dataanalysispackage_amd as fx
+import refusal_cases as R
+from eeg_dataanalysispackage_amd import _lib
+from eeg_dataanalysispackage_amd._lib import ptr
 from eeg_dataanalysispackage_amd.brainvision import EEGMarker
 from conftest import DOD01, DOD02
 
@@ -23,8 +28,10 @@ def markers(pos, stim):
 
 
 @pytest.mark.parametrize("n,seed,balance", [(1, 0, 0), (7, 1, 1), (1000, 2, -1),
-                                            (200_003, 3, 0), (1_000_000, 4, 1)])
+                                            (200_003, 3, 0), (1_000_000, 4, 1),
+                                            (R.PLAN_BIG_N, 5, -1)])
 def test_scan_equals_sequential(ctx, n, seed, balance):
+    """R.PLAN_BIG_N: past one trip of the three plan kernels' capped grid (8192 x 256 markers)."""
     rng = np.random.default_rng(seed)
     nf = 10 * n + 5000
     pos = rng.integers(-50, nf + 300, size=n)      # some cuts leave the recording
@@ -70,6 +77,28 @@ def test_reference_recordings(ctx, base, guessed):
     assert np.array_equal(dp, hp) and np.array_equal(dl, hl) and db == hb
 
 
+def raw_plan(ctx, pos, stim, nf, guessed, balance, mem):
+    """eegfx_plan_markers_device itself: (status, message, balance, n_selected, pos_out,
+    label_out), the outputs as the call left them (filled with -9 before it)."""
+    import torch
+    n = len(pos)
+    bal, k = c_int64(balance), c_int64(-7)
+    if mem == _lib.MEM_DEVICE:
+        p, s = torch.from_numpy(pos).cuda(), torch.from_numpy(stim).cuda()
+        po = torch.full((n,), -9, dtype=torch.int64, device="cuda")
+        lo = torch.full((n,), -9.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+    else:
+        p, s = pos, stim
+        po, lo = np.full(n, -9, dtype=np.int64), np.full(n, -9.0)
+    rc = fx.lib().eegfx_plan_markers_device(ctx.handle, ptr(p), ptr(s), n, nf, guessed, byref(bal),
+                                            ptr(po), ptr(lo), byref(k), mem)
+    msg = fx.lib().eegfx_last_error().decode()
+    if mem == _lib.MEM_DEVICE:
+        po, lo = po.cpu().numpy(), lo.cpu().numpy()
+    return rc, msg, bal.value, k.value, po, lo
+
+
 def test_unparsable_description_keeps_prefix(ctx):
     pos = np.arange(200, 2200, 100, dtype=np.int64)
     stim = np.array([0, 1] * 10, dtype=np.int32)
@@ -79,3 +108,35 @@ def test_unparsable_description_keeps_prefix(ctx):
     assert e.value.args[0] in (-3, "EFORMAT") or "EFORMAT" in str(e.value)
     with pytest.raises(fx.EegfxError):
         ctx.plan_markers(pos, stim, 10_000, 1, balance=2)
+    # Integer.parseInt's NumberFormatException ends the reference's loop at the first such marker:
+    # what it selected before that is what the C ABI leaves behind (R.PLAN_CASES: no marker before
+    # it, one offender, two lanes of one wave, two workgroups of the capped grid's second trip)
+    for n, offenders in R.PLAN_CASES:
+        rng = np.random.default_rng(n + len(offenders))
+        nf = 10 * n + 5000
+        pos = rng.integers(-50, nf + 300, size=n)
+        stim = rng.integers(-1, 6, size=n).astype(np.int32)
+        stim[list(offenders)] = np.iinfo(np.int32).min
+        first = offenders[0]
+        for balance in (0, 1):
+            hp, hl, hb = host_plan(pos[:first], stim[:first], nf, 3, balance)
+            if first <= R.PLAN_SMALL_N:   # the restatement is the host planner's (the goldens')
+                fp, fl, fb = fx.plan_markers(markers(pos[:first], stim[:first]), nf, 3, balance)
+                assert np.array_equal(fp, hp) and np.array_equal(fl, hl) and fb == hb
+            if first == 0:
+                assert hp.size == 0 and hb == balance     # nothing planned, balance as given
+            for mem in (_lib.MEM_HOST, _lib.MEM_DEVICE):
+                rc, msg, bal, k, po, lo = raw_plan(ctx, pos, stim, nf, 3, balance, mem)
+                what = (n, offenders, balance, mem)
+                assert rc == _lib.EEGFX_EFORMAT and f"marker {first}:" in msg, what
+                assert (k, bal) == (hp.size, hb), what
+                assert np.array_equal(po[:k], hp) and np.array_equal(lo[:k], hl), what
+                assert (po[k:] == -9).all() and (lo[k:] == -9.0).all(), what
+    # a clean call through the same door returns the whole plan
+    pos = np.arange(200, 2200, 100, dtype=np.int64)
+    stim = np.array([0, 1] * 10, dtype=np.int32)
+    hp, hl, hb = host_plan(pos, stim, 10_000, 1, 0)
+    for mem in (_lib.MEM_HOST, _lib.MEM_DEVICE):
+        rc, _, bal, k, po, lo = raw_plan(ctx, pos, stim, 10_000, 1, 0, mem)
+        assert (rc, k, bal) == (_lib.EEGFX_OK, hp.size, hb)
+        assert np.array_equal(po[:k], hp) and np.array_equal(lo[:k], hl)
