@@ -8,6 +8,8 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
 * :class:`DecisionTreeClassifier`, :func:`dtree_train`, :func:`dtree_predict` -- train_clf=dt
 * :class:`RandomForestClassifier`, :func:`rforest_train`, :func:`rforest_predict`,
   :func:`poisson_bag` -- train_clf=rf
+* :class:`NeuralNetworkClassifier`, :func:`nn_config_from`, :func:`nn_init_params`,
+  :func:`nn_train`, :func:`nn_predict`, :func:`nn_statistics` -- train_clf=nn
   (the other classifiers live in :mod:`classification`; :func:`pipeline.run_train_clf` is the
   train/test flow over ``OffLineDataProvider.split`` with the rows resident on the device)
 * :mod:`brainvision` -- native .vhdr/.vmrk reader and marker planner
@@ -15,16 +17,19 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
 from ._lib import EegfxError, LIB_PATH, lib
 from .brainvision import (ChannelInfo, EEGMarker, Header, plan_markers, read_header,
                           read_markers, read_raw, recording_frames)
-from .classification import (DecisionTreeClassifier, RandomForestClassifier, dtree_predict,
-                             dtree_train, poisson_bag, rforest_predict, rforest_train)
+from .classification import (DecisionTreeClassifier, NeuralNetworkClassifier,
+                             RandomForestClassifier, dtree_predict, dtree_train, nn_config_from,
+                             nn_init_params, nn_predict, nn_statistics, nn_train, poisson_bag,
+                             rforest_predict, rforest_train)
 from .context import Context, device_count
 from .data_provider import OffLineDataProvider
 from .feature_extraction import IFeatureExtraction, WaveletTransform
 
 __all__ = [
     "Context", "ChannelInfo", "DecisionTreeClassifier", "EEGMarker", "EegfxError", "Header",
-    "IFeatureExtraction", "LIB_PATH", "OffLineDataProvider", "RandomForestClassifier",
-    "WaveletTransform", "device_count", "dtree_predict", "dtree_train", "lib",
+    "IFeatureExtraction", "LIB_PATH", "NeuralNetworkClassifier", "OffLineDataProvider",
+    "RandomForestClassifier", "WaveletTransform", "device_count", "dtree_predict", "dtree_train",
+    "lib", "nn_config_from", "nn_init_params", "nn_predict", "nn_statistics", "nn_train",
     "plan_markers", "poisson_bag", "read_header", "read_markers", "read_raw", "recording_frames",
     "rforest_predict", "rforest_train",
 ]

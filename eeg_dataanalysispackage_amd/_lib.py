@@ -80,6 +80,20 @@ class TreeNode(Structure):
                 ("gain", c_double)]
 
 
+NN_MAX_LAYERS = 4
+NN_MAX_WIDTH = 64
+NN_ACTIVATIONS = {"sigmoid": 0, "tanh": 1, "relu": 2, "identity": 3, "softplus": 4, "elu": 5,
+                  "softmax": 6}
+NN_LOSSES = {"mse": 0, "xent": 1, "negativeloglikelihood": 2, "squared_loss": 3}
+NN_UPDATERS = {"nesterovs": 0, "sgd": 1, "adam": 2, "adagrad": 3, "rmsprop": 4}
+
+
+class NnConfig(Structure):
+    _fields_ = [("n_layers", c_int32), ("n_out", c_int32 * NN_MAX_LAYERS),
+                ("activation", c_int32 * NN_MAX_LAYERS), ("loss", c_int32), ("updater", c_int32),
+                ("num_iterations", c_int32), ("learning_rate", c_double), ("momentum", c_double)]
+
+
 class EegfxError(RuntimeError):
     """A non-zero status of the C ABI (carries the code and eegfx_last_error())."""
 
@@ -200,6 +214,13 @@ SIGNATURES = {
     "eegfx_confusion_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int]),
     "eegfx_odp_split": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int32, c_int32, c_int32,
                                 c_int32, c_void_p, c_void_p, POINTER(c_int64), c_int]),
+    "eegfx_nn_param_count": (c_int64, [c_int32, POINTER(NnConfig)]),
+    "eegfx_nn_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(NnConfig),
+                               c_void_p, c_void_p, c_void_p, c_int]),
+    "eegfx_nn_predict": (c_int, [c_void_p, c_void_p, c_int64, c_int32, POINTER(NnConfig), c_void_p,
+                                 c_void_p, c_int]),
+    "eegfx_nn_statistics": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_int]),
 }
 
 _lib = None

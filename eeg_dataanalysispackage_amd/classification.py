@@ -13,19 +13,24 @@ count actual-1 / predicted-0).  ``SVMClassifier`` is the same flow with MLlib 1.
 (``eegfx_dtree_train`` / ``eegfx_dtree_predict``), and
 ``RandomForestClassifier`` (train_clf=rf) with MLlib 1.6.2 ``RandomForest``
 (``eegfx_rforest_train`` / ``eegfx_rforest_predict``).
+``NeuralNetworkClassifier`` (train_clf=nn) is the dense network the reference builds with DL4J from
+its ``config_layer<i>_*`` keys, as DESIGN.md section 10.7 defines it (``eegfx_nn_train`` /
+``eegfx_nn_predict`` / ``eegfx_nn_statistics``); its statistics follow
+``ClassificationStatistics.add``, not Spark's confusion matrix.
 Model save/load (Spark model directories) is out of scope.
 """
 from __future__ import annotations
 
 import math
 from ctypes import byref, c_int32, c_int64
-from typing import Dict, Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import EegfxError, lib, ptr
-from .context import Context, _contig, _is_device, _mem
+from .context import Context, _check_out, _contig, _is_device, _mem
 
 # LogisticRegressionWithSGD() defaults (MLlib 1.6.2) and GradientDescent's convergence tolerance
 DEFAULT_STEP_SIZE = 1.0
@@ -264,11 +269,17 @@ class ClassificationStatistics:
     """Utils/ClassificationStatistics.java (the counters the classifiers report)."""
 
     def __init__(self, truePositives: int = 0, trueNegatives: int = 0, falsePositives: int = 0,
-                 falseNegatives: int = 0):
+                 falseNegatives: int = 0, MSE: Optional[float] = None,
+                 class1sum: Optional[float] = None, class2sum: Optional[float] = None):
         self.truePositives = int(truePositives)
         self.trueNegatives = int(trueNegatives)
         self.falsePositives = int(falsePositives)
         self.falseNegatives = int(falseNegatives)
+        # what add() accumulates besides the counters (train_clf=nn); printed only when set
+        self._has_sums = not (MSE is None and class1sum is None and class2sum is None)
+        self.MSE = float(MSE or 0.0)
+        self.class1sum = float(class1sum or 0.0)
+        self.class2sum = float(class2sum or 0.0)
 
     def getNumberOfPatterns(self) -> int:
         return self.truePositives + self.trueNegatives + self.falsePositives + self.falseNegatives
@@ -281,11 +292,16 @@ class ClassificationStatistics:
         return (self.truePositives, self.trueNegatives, self.falsePositives, self.falseNegatives)
 
     def __repr__(self) -> str:
-        return (f"Number of patterns: {self.getNumberOfPatterns()}\n"
+        text = (f"Number of patterns: {self.getNumberOfPatterns()}\n"
                 f"True positives: {self.truePositives}\nTrue negatives: {self.trueNegatives}\n"
                 f"False positives: {self.falsePositives}\n"
                 f"False negatives: {self.falseNegatives}\n"
                 f"Accuracy: {self.calcAccuracy() * 100}%\n")
+        if self._has_sums:
+            n = self.getNumberOfPatterns()
+            text += (f"MSE: {self.MSE / n if n else math.nan}\n"
+                     f"Non-targets: {self.class1sum}\nTargets: {self.class2sum}\n")
+        return text
 
 
 def reference_statistics(predictions, labels) -> ClassificationStatistics:
@@ -516,7 +532,313 @@ class RandomForestClassifier(DecisionTreeClassifier):
         return rforest_predict(self.context, features, self.nodes, self.tree_offsets)
 
 
+# ---- train_clf=nn (NeuralNetworkClassifier.java) ------------------------
+NN_LAYER_KEYS = ("layer_type", "drop_out", "activation_function", "n_out")
+NN_GLOBAL_KEYS = ("config_seed", "config_num_iterations", "config_learning_rate",
+                  "config_momentum", "config_weight_init", "config_updater",
+                  "config_optimization_algo", "config_loss_function", "config_pretrain",
+                  "config_backprop")
+NN_WEIGHT_INITS = ("xavier", "zero", "sigmoid", "uniform", "relu")
+
+
+@dataclass(frozen=True)
+class NnModel:
+    """A checked train_clf=nn model: d features, the layers' widths and activation names, the
+    loss and updater names (unknown strings already mapped as the reference's parse* do), and the
+    training settings."""
+    d: int
+    widths: Tuple[int, ...]
+    activations: Tuple[str, ...]
+    loss: str = "mse"
+    updater: str = "nesterovs"
+    learning_rate: float = 0.1
+    momentum: float = 0.5
+    num_iterations: int = 1000
+    seed: int = 12345
+    weight_init: str = "xavier"
+
+    def struct(self, num_iterations: Optional[int] = None) -> "_lib.NnConfig":
+        c = _lib.NnConfig()
+        c.n_layers = len(self.widths)
+        for i, (w, a) in enumerate(zip(self.widths[:_lib.NN_MAX_LAYERS], self.activations)):
+            c.n_out[i] = int(w)
+            c.activation[i] = _lib.NN_ACTIVATIONS[a]
+        c.loss = _lib.NN_LOSSES[self.loss]
+        c.updater = _lib.NN_UPDATERS[self.updater]
+        c.num_iterations = int(self.num_iterations if num_iterations is None else num_iterations)
+        c.learning_rate = float(self.learning_rate)
+        c.momentum = float(self.momentum)
+        return c
+
+    def layer_shapes(self):
+        """(n_in, n_out) of every layer."""
+        n_in = (self.d,) + tuple(self.widths[:-1])
+        return list(zip(n_in, self.widths))
+
+    @property
+    def param_count(self) -> int:
+        """eegfx_nn_param_count (host only): raises EegfxError for a model the library refuses."""
+        n = lib().eegfx_nn_param_count(int(self.d), byref(self.struct()))
+        if n < 0:
+            _lib.check(int(n))
+        return int(n)
+
+
+def _nn_refuse(code, key, value, why):
+    raise EegfxError(code, f"{key}={value}: {why}")
+
+
+def nn_config_from(config: Dict[str, str], d: int) -> NnModel:
+    """The model NeuralNetworkClassifier.java:102-137, 258-320 builds from the config_* keys, or
+    EegfxError naming the key and the value for what this library does not train.  Layer i = 1..L
+    reads config_layer<i>_{layer_type, drop_out, activation_function, n_out}; L = the number of
+    config_layer* keys // 4.  Unknown strings map as the reference's parse* map them (activation ->
+    sigmoid, loss -> mse, updater -> nesterovs, weight init -> relu, optimization algorithm ->
+    stochastic_gradient_descent, layer type -> output).  Refused: a missing key (the reference
+    dies on null), auto_encoder / rbm / graves_lstm layers, a dense last layer or an output layer
+    that is not last, dropout, the line-search optimisers, pretrain=true, backprop other than
+    true, more than 4 layers, hidden widths outside [1, 64], an output width other than 2."""
+    def get(key):
+        if key not in config or config[key] is None:
+            raise EegfxError(_lib.EEGFX_EINVAL, f"{key} is missing (the reference dies on null)")
+        return str(config[key])
+
+    def number(key, kind):
+        try:
+            return kind(get(key))
+        except ValueError:
+            _nn_refuse(_lib.EEGFX_EINVAL, key, get(key), f"not {kind.__name__}")
+
+    for key in NN_GLOBAL_KEYS:
+        get(key)
+    n_layers = sum(1 for k in config if k.startswith("config_layer")) // 4
+    if not 1 <= n_layers <= _lib.NN_MAX_LAYERS:
+        raise EegfxError(_lib.EEGFX_EINVAL,
+                         f"{n_layers} layers (the config_layer* keys // 4): 1 to "
+                         f"{_lib.NN_MAX_LAYERS} are supported")
+    algo = get("config_optimization_algo")
+    if algo in ("line_gradient_descent", "lbfgs", "conjugate_gradient"):
+        _nn_refuse(_lib.EEGFX_ENOTSUP, "config_optimization_algo", algo,
+                   "only stochastic_gradient_descent is trained")
+    if get("config_pretrain") == "true":
+        _nn_refuse(_lib.EEGFX_ENOTSUP, "config_pretrain", "true", "no layer here pretrains")
+    if get("config_backprop") != "true":
+        _nn_refuse(_lib.EEGFX_ENOTSUP, "config_backprop", get("config_backprop"),
+                   "without backprop nothing is trained")
+    widths, acts = [], []
+    for i in range(1, n_layers + 1):
+        pre = f"config_layer{i}_"
+        kind = get(pre + "layer_type")
+        if kind in ("auto_encoder", "rbm", "graves_lstm"):
+            _nn_refuse(_lib.EEGFX_ENOTSUP, pre + "layer_type", kind,
+                       "only dense and output layers are trained")
+        if kind == "dense" and i == n_layers:
+            _nn_refuse(_lib.EEGFX_EINVAL, pre + "layer_type", kind,
+                       "the last layer must be an output layer")
+        if kind != "dense" and i < n_layers:
+            _nn_refuse(_lib.EEGFX_EINVAL, pre + "layer_type", kind,
+                       "an output layer must be the last layer")
+        if kind in ("dense", "output"):  # the default branch of parseLayer reads no drop_out
+            drop = number(pre + "drop_out", float)
+            if drop != 0.0:
+                _nn_refuse(_lib.EEGFX_ENOTSUP, pre + "drop_out", get(pre + "drop_out"),
+                           "dropout is not trained")
+        width = number(pre + "n_out", int)
+        if i < n_layers and not 1 <= width <= _lib.NN_MAX_WIDTH:
+            _nn_refuse(_lib.EEGFX_EINVAL, pre + "n_out", width,
+                       f"a dense layer's width lies in [1, {_lib.NN_MAX_WIDTH}]")
+        if i == n_layers and width != 2:
+            _nn_refuse(_lib.EEGFX_EINVAL, pre + "n_out", width,
+                       "the output layer's n_out must be 2 (the labels are {t, |1 - t|})")
+        act = get(pre + "activation_function")
+        widths.append(width)
+        acts.append(act if act in _lib.NN_ACTIVATIONS else "sigmoid")
+    loss = get("config_loss_function")
+    updater = get("config_updater")
+    init = get("config_weight_init")
+    iterations = number("config_num_iterations", int)
+    if iterations < 0:
+        _nn_refuse(_lib.EEGFX_EINVAL, "config_num_iterations", iterations, "negative")
+    return NnModel(d=int(d), widths=tuple(widths), activations=tuple(acts),
+                   loss=loss if loss in _lib.NN_LOSSES else "mse",
+                   updater=updater if updater in _lib.NN_UPDATERS else "nesterovs",
+                   learning_rate=number("config_learning_rate", float),
+                   momentum=number("config_momentum", float), num_iterations=iterations,
+                   seed=number("config_seed", int),
+                   weight_init=init if init in NN_WEIGHT_INITS else "relu")
+
+
+def nn_init_params(model: NnModel) -> np.ndarray:
+    """The initial flat parameter vector (layer after layer: W[n_in][n_out] row-major, then
+    b[n_out] = 0), drawn on the host.  ND4J's stream cannot be restated, so the generator is this
+    one: ``rng = numpy.random.Generator(numpy.random.PCG64(seed & 0xFFFFFFFF))``; for each layer
+    in order its n_in * n_out weights come from one call, in row-major order --
+    xavier: ``rng.standard_normal(k) * sqrt(2 / (n_in + n_out))``;
+    relu: ``rng.standard_normal(k) * sqrt(2 / n_in)``;
+    sigmoid: ``rng.uniform(-a, a, k)`` with a = 4 sqrt(6 / (n_in + n_out));
+    uniform: ``rng.uniform(-a, a, k)`` with a = 1 / sqrt(n_in); zero: zeros (no draw)."""
+    rng = np.random.Generator(np.random.PCG64(int(model.seed) & 0xFFFFFFFF))
+    parts = []
+    for n_in, n_out in model.layer_shapes():
+        k = n_in * n_out
+        if model.weight_init == "xavier":
+            w = rng.standard_normal(k) * math.sqrt(2.0 / (n_in + n_out))
+        elif model.weight_init == "sigmoid":
+            a = 4.0 * math.sqrt(6.0 / (n_in + n_out))
+            w = rng.uniform(-a, a, k)
+        elif model.weight_init == "uniform":
+            a = 1.0 / math.sqrt(n_in)
+            w = rng.uniform(-a, a, k)
+        elif model.weight_init == "zero":
+            w = np.zeros(k)
+        else:
+            w = rng.standard_normal(k) * math.sqrt(2.0 / n_in)
+        parts += [w, np.zeros(n_out)]
+    return np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)
+
+
+def nn_train(ctx: Context, X, y, model: NnModel, params0=None, num_iterations=None,
+             params_out=None, scores_out=None):
+    """model.num_iterations (or num_iterations) full-batch iterations on the device
+    (eegfx_nn_train) from params0 (default nn_init_params(model)); returns (params, scores):
+    the trained flat vector and the loss before each iteration's step.  X (n x d float64) and y
+    (n labels 0/1) are both host arrays or both device tensors; the results are host arrays
+    (params_out / scores_out: caller's float64 buffers to fill instead of new ones)."""
+    X, y, n, d, mem = _train_inputs(X, y)
+    if d != model.d:
+        raise ValueError(f"X has {d} features, the model {model.d}")
+    cfg = model.struct(num_iterations)
+    count = model.param_count
+    p0 = np.ascontiguousarray(nn_init_params(model) if params0 is None else params0,
+                              dtype=np.float64)
+    if p0.shape != (count,):
+        raise ValueError(f"params0 must hold {count} parameters, got {p0.shape}")
+    out = (np.empty(count, dtype=np.float64) if params_out is None
+           else _check_out(params_out, (count,)))
+    scores = (np.empty(max(cfg.num_iterations, 0), dtype=np.float64) if scores_out is None
+              else _check_out(scores_out, (max(cfg.num_iterations, 0),)))
+    ctx._call(mem, X, lib().eegfx_nn_train, ctx.handle, ptr(X), ptr(y), n, d, byref(cfg), ptr(p0),
+              ptr(out), ptr(scores), mem)
+    return out, scores
+
+
+def nn_predict(ctx: Context, X, model: NnModel, params, out=None):
+    """Output 0 of the last layer for every row of X (eegfx_nn_predict): the score of "target"
+    the reference reads with model.output(features).getDouble(0); on X's side."""
+    p = np.ascontiguousarray(params, dtype=np.float64)
+    X, fresh, mem, n, d = _predict_inputs(X)
+    if out is None:
+        out = fresh
+    else:
+        mem = _mem(X, _check_out(out, (n,)))
+    if d != model.d or p.shape != (model.param_count,):
+        raise ValueError("X or params do not fit the model")
+    cfg = model.struct()
+    ctx._call(mem, X, lib().eegfx_nn_predict, ctx.handle, ptr(X), n, d, byref(cfg), ptr(p),
+              ptr(out), mem)
+    return out
+
+
+def java_round(x: float) -> int:
+    """Java 7+ Math.round(double): floor(x + 1/2) without the rounding error of the addition,
+    NaN -> 0, saturating at Long.MIN_VALUE / MAX_VALUE."""
+    x = float(x)
+    if x != x:
+        return 0
+    if x >= 2.0 ** 63:
+        return 2 ** 63 - 1
+    if x <= -2.0 ** 63:
+        return -2 ** 63
+    f = math.floor(x)
+    return f + (1 if x - f >= 0.5 else 0)
+
+
+def reference_nn_statistics(scores, labels) -> ClassificationStatistics:
+    """Utils/ClassificationStatistics.add(score, label) over the pairs, in order (:68-83): a label
+    that rounds to 0 is a true negative if the score rounds to 0, else a false positive; a label
+    that rounds to 1 a true positive if the score rounds to 1, else a false negative (a score
+    that rounds to 2 or -1 is a miss, not dropped); MSE, class1sum and class2sum accumulate."""
+    tp = tn = fp = fn = 0
+    mse = c1 = c2 = 0.0
+    for s, a in zip(np.asarray(scores, dtype=np.float64).tolist(),
+                    np.asarray(labels, dtype=np.float64).tolist()):
+        mse += (a - s) * (a - s)
+        want, got = java_round(a), java_round(s)
+        if want == 0:
+            tn, fp = tn + (got == 0), fp + (got != 0)
+            c1 += s
+        elif want == 1:
+            tp, fn = tp + (got == 1), fn + (got != 1)
+            c2 += s
+    return ClassificationStatistics(tp, tn, fp, fn, MSE=mse, class1sum=c1, class2sum=c2)
+
+
+def nn_statistics(ctx: Context, scores, labels) -> ClassificationStatistics:
+    """reference_nn_statistics counted on the device in one pass (eegfx_nn_statistics): the four
+    counters are exact, the three sums are added in the kernel's fixed order.  scores and labels
+    are both host arrays or both device tensors."""
+    if _is_device(scores) != _is_device(labels):
+        raise ValueError("scores and labels must both be host or both be device arrays")
+    s = _contig(scores, np.float64)
+    a = _contig(labels, np.float64)
+    n = int(s.shape[0])
+    if s.ndim != 1 or a.ndim != 1 or int(a.shape[0]) != n:
+        raise ValueError(f"scores and labels must be [n], got {tuple(s.shape)} and "
+                         f"{tuple(a.shape)}")
+    counts = np.zeros(4, dtype=np.int64)
+    sums = np.zeros(3, dtype=np.float64)
+    mem = _mem(s, a)
+    ctx._call(mem, s, lib().eegfx_nn_statistics, ctx.handle, ptr(s), ptr(a), n, ptr(counts),
+              ptr(sums), mem)
+    return ClassificationStatistics(*(int(v) for v in counts), MSE=float(sums[0]),
+                                    class1sum=float(sums[1]), class2sum=float(sums[2]))
+
+
+class NeuralNetworkClassifier(_Classifier):
+    """IClassifier for train_clf=nn (NeuralNetworkClassifier.java), GPU-resident: the dense
+    network of DESIGN.md section 10.7.  ``model`` (NnModel), ``params`` (the flat vector) and
+    ``scores`` (the loss per iteration) are set by training."""
+
+    def __init__(self, context: Optional[Context] = None):
+        super().__init__(context)
+        self.model: Optional[NnModel] = None
+        self.params: Optional[np.ndarray] = None
+        self.scores: Optional[np.ndarray] = None
+
+    def _trained(self) -> bool:
+        return self.params is not None
+
+    def trainFeatures(self, X, y) -> None:
+        """:69-149 -- the network of the config_* keys (nn_config_from: every key is required, as
+        in the reference), initialised by nn_init_params from config_seed and config_weight_init,
+        fitted by config_num_iterations full-batch iterations."""
+        self.model = nn_config_from(self.config, int(X.shape[1]))
+        self.params, self.scores = nn_train(self.context, X, y, self.model)
+
+    def _predict_rows(self, features):
+        return nn_predict(self.context, features, self.model, self.params)
+
+    def test(self, epochs, targets: Sequence[float]) -> ClassificationStatistics:
+        """:152-168 -- resultsStats.add(output, target) per epoch."""
+        if not self._trained():
+            raise RuntimeError("The classifier has not been trained")
+        return reference_nn_statistics(self.predict(self._features(epochs)), targets)
+
+    def testFeatures(self, X, y) -> ClassificationStatistics:
+        """test() on feature rows that exist already: the scores of device rows stay on the device
+        and are counted there (nn_statistics); host rows go through reference_nn_statistics."""
+        scores = self.predict(X)
+        if not _is_device(scores):
+            return reference_nn_statistics(scores, y)
+        if not _is_device(y):
+            import torch
+            y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float64), device=scores.device)
+        return nn_statistics(self.context, scores, y)
+
+
 __all__ = ["ClassificationStatistics", "DecisionTreeClassifier", "LogisticRegressionClassifier",
-           "RandomForestClassifier", "SVMClassifier", "confusion_counts", "dtree_predict",
+           "NeuralNetworkClassifier", "NnModel", "RandomForestClassifier", "SVMClassifier",
+           "java_round", "nn_config_from", "nn_init_params", "nn_predict", "nn_statistics",
+           "nn_train", "reference_nn_statistics", "confusion_counts", "dtree_predict",
            "dtree_train", "poisson_bag", "predict", "reference_statistics", "rforest_predict",
            "rforest_train", "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]

@@ -1,8 +1,8 @@
 // ctx.h -- the device context (struct eegfx_ctx) and the helpers that the host sources share:
 // the staging of host-memory arguments (stage_in, dev_out, copy_out and what is built on them),
 // the argument checks (defined in api.cpp) and the device-pointer pipelines (routes.cpp), used by
-// api.cpp, routes.cpp, streamed.cpp, classify.cpp, tree_driver.cpp, mailbox.cpp, flow.cpp and
-// odp.cpp (the OffLineDataProvider).
+// api.cpp, routes.cpp, streamed.cpp, classify.cpp, nn.cpp, tree_driver.cpp, mailbox.cpp, flow.cpp
+// and odp.cpp (the OffLineDataProvider).
 // Internal: not installed.
 #pragma once
 
@@ -195,6 +195,10 @@ struct eegfx_ctx {
   // (eegfx_confusion_counts); the indices, the gathered rows (gather, split); labels in (split,
   // confusion); labels out (split); the kernels' flag / counter block (all three).
   DevBuf fl_src, fl_idx, fl_dst, fl_lab, fl_y, fl_flag;
+  // eegfx_nn_*: NnState with the parameters and the updater's state (train; predict: the
+  // parameters), the gradient partials, the loss per iteration; eegfx_nn_statistics: a host
+  // caller's scores (its labels go to row_vals), the counters followed by the partial sums.
+  DevBuf nn_state, nn_part, nn_scores, nn_in, nn_stat;
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
   PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
                                          // a sharded provider's worker: the file spans it reads
@@ -226,7 +230,7 @@ struct eegfx_ctx {
     return std::array{&raw, &pos, &out, &scratch, &fused, &rows_x, &row_vals, &lr_state, &lr_part,
                       &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_nodes,
                       &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
-                      &fl_flag};
+                      &fl_flag, &nn_state, &nn_part, &nn_scores, &nn_in, &nn_stat};
   }
   void bind_buffers() {
     for (DevBuf* b : buffers()) b->sp = &stream;

@@ -263,4 +263,51 @@ struct ConfusionOut {          // zeroed by the caller
 hipError_t launch_confusion(hipStream_t st, const double* pred, const double* labels, int64_t n,
                             ConfusionOut* out);
 
+// nn.hip: the dense network of train_clf=nn (eegfx_nn_*).  The codes are
+// those of eegfx.h (EEGFX_NN_ACT_*, EEGFX_NN_LOSS_*, EEGFX_NN_UPD_*).
+constexpr int kNnMaxLayers = 4;
+constexpr int kNnMaxWidth = 64;
+struct NnNet {               // the checked model
+  int32_t L, d, P;           // layers, features, parameters
+  int32_t loss, updater;
+  int32_t n_in[kNnMaxLayers], n_out[kNnMaxLayers], act[kNnMaxLayers];
+  int32_t w_off[kNnMaxLayers];  // layer l in the flat vector: W [n_in][n_out], then b [n_out]
+};
+// How a workgroup lays one tile of `rows` feature rows out in LDS (offsets and strides in
+// doubles; every stride is odd, so lanes that differ in the row meet different banks).  A
+// function of the model alone (nn_plan_tile).
+struct NnTile {
+  int32_t rows;      // feature rows per tile
+  int32_t w1_lds;    // 1: layer 1's weights are staged in LDS; 0: read through L2 (wide d)
+  int32_t doubles;   // LDS of the workgroup
+  int32_t x_off, x_stride;   // the rows' features [rows][x_stride]
+  int32_t y_off, loss_off;   // label / loss of each row
+  int32_t w_lds[kNnMaxLayers], w_stride[kNnMaxLayers], b_lds[kNnMaxLayers];
+  int32_t a_off[kNnMaxLayers], z_off[kNnMaxLayers], a_stride[kNnMaxLayers];
+};
+struct NnState {     // followed by double params[P], s1[P], s2[P] (the updater's state)
+  int32_t iter;      // iterations done
+  int32_t flag;      // 2: label validation failed (every kernel then returns at once)
+  uint32_t ticket;   // workgroups of the running nn_update_kernel that have finished
+  int32_t pad;
+};
+inline double* nn_params(NnState* st) { return (double*)(st + 1); }
+NnTile nn_plan_tile(const NnNet& net);
+int nn_grid(int64_t n, const NnNet& net, const NnTile& tl);
+hipError_t launch_nn_validate(hipStream_t st, const double* y, int64_t n, NnState* state);
+// one iteration: nn_grad_kernel, then nn_update_kernel.  partial: double [G][P + 1] (the
+// workgroup's gradient sums, then its loss sum); scores: null or one loss per iteration
+hipError_t launch_nn_iteration(hipStream_t st, const double* X, const double* y, int64_t n,
+                               const NnNet& net, const NnTile& tl, int G, NnState* state,
+                               double* partial, double lr, double momentum, double* scores);
+hipError_t launch_nn_predict(hipStream_t st, const double* X, int64_t n, const NnNet& net,
+                             const NnTile& tl, const double* params, double* out);
+struct NnStatsOut {                   // zeroed by the caller
+  unsigned long long cell[4];         // tp, tn, fp, fn of ClassificationStatistics.add
+};
+int nn_stats_grid(int64_t n);
+// sums: double [grid][3] = each workgroup's (label - score)^2, class-1 and class-2 score sums
+hipError_t launch_nn_stats(hipStream_t st, const double* scores, const double* labels, int64_t n,
+                           NnStatsOut* out, double* sums);
+
 }  // namespace eegfx

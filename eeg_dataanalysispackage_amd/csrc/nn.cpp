@@ -1,0 +1,158 @@
+// nn.cpp -- the train_clf=nn drivers of the eegfx C ABI (eegfx_nn_param_count, eegfx_nn_train,
+// eegfx_nn_predict, eegfx_nn_statistics) over the kernels of nn.hip.
+#include <cstring>
+#include <vector>
+
+#include "ctx.h"
+
+namespace {
+
+// The model of a config, checked: what is refused names the reference's config key and the value.
+NnNet nn_check_model(int32_t d, const eegfx_nn_config* cfg) {
+  if (!cfg) fail(EEGFX_EINVAL, "null argument");
+  check_train_d(d);
+  const int L = cfg->n_layers;
+  if (L < 1 || L > kNnMaxLayers)
+    fail(EEGFX_EINVAL, "%d layers (the config_layer* keys / 4): 1 to %d are supported", L,
+         kNnMaxLayers);
+  NnNet net{};
+  net.L = L;
+  net.d = d;
+  int off = 0;
+  for (int l = 0; l < L; ++l) {
+    const int no = cfg->n_out[l], act = cfg->activation[l];
+    if (l < L - 1 && (no < 1 || no > kNnMaxWidth))
+      fail(EEGFX_EINVAL, "config_layer%d_n_out=%d: a dense layer's width lies in [1, %d]", l + 1,
+           no, kNnMaxWidth);
+    if (l == L - 1 && no != 2)
+      fail(EEGFX_EINVAL,
+           "config_layer%d_n_out=%d: the output layer's n_out must be 2 (the labels are "
+           "{t, |1 - t|})", l + 1, no);
+    if (act < EEGFX_NN_ACT_SIGMOID || act > EEGFX_NN_ACT_SOFTMAX)
+      fail(EEGFX_EINVAL, "config_layer%d_activation_function: code %d is no EEGFX_NN_ACT_*", l + 1,
+           act);
+    net.n_in[l] = l == 0 ? d : cfg->n_out[l - 1];
+    net.n_out[l] = no;
+    net.act[l] = act;
+    net.w_off[l] = off;
+    off += net.n_in[l] * no + no;
+  }
+  net.P = off;
+  if (cfg->loss < EEGFX_NN_LOSS_MSE || cfg->loss > EEGFX_NN_LOSS_SQUARED)
+    fail(EEGFX_EINVAL, "config_loss_function: code %d is no EEGFX_NN_LOSS_*", cfg->loss);
+  if (cfg->updater < EEGFX_NN_UPD_NESTEROVS || cfg->updater > EEGFX_NN_UPD_RMSPROP)
+    fail(EEGFX_EINVAL, "config_updater: code %d is no EEGFX_NN_UPD_*", cfg->updater);
+  net.loss = cfg->loss;
+  net.updater = cfg->updater;
+  return net;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t eegfx_nn_param_count(int32_t d, const eegfx_nn_config* cfg) {
+  int64_t count = 0;
+  const int rc = guarded([&] { count = nn_check_model(d, cfg).P; });
+  return rc == EEGFX_OK ? count : rc;
+}
+
+int eegfx_nn_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                   const eegfx_nn_config* cfg, const double* params0, double* params_out,
+                   double* scores_out, int mem) {
+  return guarded([&] {
+    if (!ctx || !cfg || !params0 || !params_out) fail(EEGFX_EINVAL, "null argument");
+    check_mem(mem);
+    if (n < 1) fail(EEGFX_EINVAL, "empty training set");
+    if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
+    const NnNet net = nn_check_model(d, cfg);
+    const int iters = cfg->num_iterations;
+    if (iters < 0) fail(EEGFX_EINVAL, "config_num_iterations=%d", iters);
+    ctx->activate();
+    const auto [dX, dy] = stage_xy(ctx, X, y, n, d, mem);
+    const size_t P = (size_t)net.P;
+    const size_t head = sizeof(NnState) + sizeof(double) * P;  // the state and the parameters
+    const size_t sbytes = head + 2 * sizeof(double) * P;       // ... and the updater's state
+    std::vector<uint8_t> hs(sbytes, 0);
+    NnState* h = (NnState*)hs.data();
+    memcpy(nn_params(h), params0, sizeof(double) * P);
+    NnState* st = (NnState*)ctx->nn_state.get(sbytes);
+    HIP_CHECK(hipMemcpyAsync(st, hs.data(), sbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(launch_nn_validate(ctx->stream, dy, n, st));
+    const NnTile tl = nn_plan_tile(net);
+    const int G = nn_grid(n, net, tl);
+    std::vector<double> scores((size_t)(scores_out ? iters : 0));
+    double* dscores = nullptr;
+    if (iters > 0) {
+      double* part = (double*)ctx->nn_part.get(sizeof(double) * (size_t)G * (P + 1));
+      if (scores_out) dscores = (double*)ctx->nn_scores.get(sizeof(double) * (size_t)iters);
+      for (int i = 0; i < iters; ++i) {
+        ctx->tic();
+        HIP_CHECK(launch_nn_iteration(ctx->stream, dX, dy, n, net, tl, G, st, part,
+                                      cfg->learning_rate, cfg->momentum, dscores));
+        ctx->toc(n * (int64_t)sizeof(double) * (d + 1));
+      }
+    }
+    HIP_CHECK(hipMemcpyAsync(hs.data(), st, head, hipMemcpyDeviceToHost, ctx->stream));
+    if (dscores)
+      HIP_CHECK(hipMemcpyAsync(scores.data(), dscores, sizeof(double) * scores.size(),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    ctx->drain();
+    if (h->flag == 2) fail(EEGFX_EINVAL, "%s", kBadLabels);
+    memcpy(params_out, nn_params(h), sizeof(double) * P);
+    if (dscores) memcpy(scores_out, scores.data(), sizeof(double) * scores.size());
+  });
+}
+
+int eegfx_nn_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
+                     const eegfx_nn_config* cfg, const double* params, double* out, int mem) {
+  return guarded([&] {
+    if (!ctx || !cfg || !params) fail(EEGFX_EINVAL, "null argument");
+    check_mem(mem);
+    check_predict_dims(n, d);
+    const NnNet net = nn_check_model(d, cfg);
+    if (n == 0) return;
+    if (!X || !out) fail(EEGFX_EINVAL, "null X / out");
+    predict_frame(ctx, X, n, d, out, mem, [&](const double* dX, double* dout) {
+      const size_t bytes = sizeof(double) * (size_t)net.P;
+      double* dp = (double*)ctx->nn_state.get(bytes);
+      HIP_CHECK(hipMemcpyAsync(dp, params, bytes, hipMemcpyHostToDevice, ctx->stream));
+      HIP_CHECK(launch_nn_predict(ctx->stream, dX, n, net, nn_plan_tile(net), dp, dout));
+    });
+  });
+}
+
+int eegfx_nn_statistics(eegfx_ctx* ctx, const double* scores, const double* labels, int64_t n,
+                        int64_t counts[4], double sums[3], int mem) {
+  return guarded([&] {
+    if (!ctx || !counts || !sums) fail(EEGFX_EINVAL, "null argument");
+    check_mem(mem);
+    if (n < 0) fail(EEGFX_EINVAL, "n=%lld", (long long)n);
+    if (n > 0 && (!scores || !labels)) fail(EEGFX_EINVAL, "null scores / labels");
+    NnStatsOut h;
+    memset(&h, 0, sizeof(h));
+    double total[3] = {0.0, 0.0, 0.0};
+    if (n > 0) {
+      ctx->activate();
+      const size_t bytes = sizeof(double) * (size_t)n;
+      const double* d_scores = stage_in(ctx, ctx->nn_in, scores, bytes, mem);
+      const double* d_labels = stage_in(ctx, ctx->row_vals, labels, bytes, mem);
+      const int G = nn_stats_grid(n);
+      std::vector<double> part((size_t)G * 3);
+      const size_t pbytes = sizeof(double) * part.size();
+      NnStatsOut* out = (NnStatsOut*)ctx->nn_stat.get(sizeof(NnStatsOut) + pbytes);
+      double* d_part = (double*)(out + 1);
+      HIP_CHECK(hipMemsetAsync(out, 0, sizeof(*out), ctx->stream));
+      HIP_CHECK(launch_nn_stats(ctx->stream, d_scores, d_labels, n, out, d_part));
+      HIP_CHECK(hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(part.data(), d_part, pbytes, hipMemcpyDeviceToHost, ctx->stream));
+      ctx->drain();
+      for (int b = 0; b < G; ++b)  // the workgroups' sums, in workgroup order
+        for (int k = 0; k < 3; ++k) total[k] += part[(size_t)b * 3 + k];
+    }
+    for (int k = 0; k < 4; ++k) counts[k] = (int64_t)h.cell[k];
+    for (int k = 0; k < 3; ++k) sums[k] = total[k];
+  });
+}
+
+}  // extern "C"

@@ -646,6 +646,73 @@ int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_f
                     int32_t name, int32_t epoch_size, int32_t skip, int32_t feature_size,
                     double* X, double* y, int64_t* n_train, int mem);
 
+/* ---- train_clf=nn: the dense network of NeuralNetworkClassifier.java on the device ------------
+ * DESIGN.md section 10.7 holds the definition; DL4J itself is not reproduced bit for bit (it
+ * computes in float32 and draws its initial weights from ND4J's stream).  Everything is float64.
+ *
+ * The model: n_layers (1..4) layers; layer l maps n_in (d for the first, the previous layer's
+ * n_out otherwise) to n_out[l] units, a = f(x W + b) with f = activation[l].  Hidden widths lie in
+ * [1, 64]; the last layer's n_out must be 2 (the reference fits labels {t, |1 - t|}).  The
+ * parameters are one flat double vector, layer after layer, each W[n_in][n_out] row-major followed
+ * by b[n_out]; the count of it is what the param_count entry returns (a pure host function;
+ * a negative status for a model that is refused, the text in eegfx_last_error()).
+ *
+ * eegfx_nn_train: num_iterations full-batch iterations from params0 (host memory, as params_out
+ * and scores_out are): the gradient of `loss` over the two outputs against {y, |1 - y|}, summed
+ * over the rows and divided by n, then p <- p - u with the updater's u (lr = learning_rate,
+ * mu = momentum):
+ *   SGD        u = lr g
+ *   NESTEROVS  v' = mu v - lr g; u = mu v - (1 + mu) v'
+ *   ADAM       (0.9, 0.999, 1e-8) u = lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps)
+ *   ADAGRAD    (1e-6) h += g^2; u = lr g / (sqrt(h) + eps)
+ *   RMSPROP    (0.95, 1e-8) r = 0.95 r + 0.05 g^2; u = lr g / sqrt(r + eps)
+ * scores_out (may be NULL): the loss before each iteration's step, num_iterations doubles.
+ * num_iterations == 0 returns params0.  A label other than 0.0 / 1.0 is EEGFX_EINVAL and leaves
+ * params_out and scores_out alone; non-finite features are trained on (they make the parameters
+ * they reach non-finite).  The sums run in an order fixed by (n, d, the widths): two calls give the
+ * same bits, from host or device rows.  X [n][d] and y [n] live on the side `mem` names, 1 <= d <=
+ * 1024, n >= 1.  The call synchronises.
+ *
+ * eegfx_nn_predict: out[r] = output 0 of the last layer for row r (the reference's
+ * model.output(features).getDouble(0)); X and out on the side `mem` names, params host memory.
+ *
+ * eegfx_nn_statistics: Utils/ClassificationStatistics.add(score, label) over n pairs, with
+ * round = Java's Math.round: a label that rounds to 0 counts a true negative if the score rounds
+ * to 0, else a false positive, and adds the score to sums[1]; a label that rounds to 1 counts a
+ * true positive if the score rounds to 1, else a false negative, and adds the score to sums[2];
+ * any other label counts nowhere.  sums[0] = the sum of (label - score)^2 over all pairs.
+ * counts = {tp, tn, fp, fn}; counts and sums are host memory, scores and labels on the side `mem`
+ * names.  n == 0 gives zeros.  The call synchronises. */
+#define EEGFX_NN_MAX_LAYERS 4
+#define EEGFX_NN_MAX_WIDTH 64
+enum {
+  EEGFX_NN_ACT_SIGMOID = 0, EEGFX_NN_ACT_TANH = 1, EEGFX_NN_ACT_RELU = 2,
+  EEGFX_NN_ACT_IDENTITY = 3, EEGFX_NN_ACT_SOFTPLUS = 4, EEGFX_NN_ACT_ELU = 5,
+  EEGFX_NN_ACT_SOFTMAX = 6
+};
+enum { EEGFX_NN_LOSS_MSE = 0, EEGFX_NN_LOSS_XENT = 1, EEGFX_NN_LOSS_NLL = 2,
+       EEGFX_NN_LOSS_SQUARED = 3 };
+enum { EEGFX_NN_UPD_NESTEROVS = 0, EEGFX_NN_UPD_SGD = 1, EEGFX_NN_UPD_ADAM = 2,
+       EEGFX_NN_UPD_ADAGRAD = 3, EEGFX_NN_UPD_RMSPROP = 4 };
+typedef struct {
+  int32_t n_layers;
+  int32_t n_out[EEGFX_NN_MAX_LAYERS];
+  int32_t activation[EEGFX_NN_MAX_LAYERS]; /* EEGFX_NN_ACT_* */
+  int32_t loss;                            /* EEGFX_NN_LOSS_* */
+  int32_t updater;                         /* EEGFX_NN_UPD_* */
+  int32_t num_iterations;
+  double learning_rate;
+  double momentum;
+} eegfx_nn_config;
+int64_t eegfx_nn_param_count(int32_t d, const eegfx_nn_config* cfg);
+int eegfx_nn_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                   const eegfx_nn_config* cfg, const double* params0, double* params_out,
+                   double* scores_out, int mem);
+int eegfx_nn_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
+                     const eegfx_nn_config* cfg, const double* params, double* out, int mem);
+int eegfx_nn_statistics(eegfx_ctx* ctx, const double* scores, const double* labels, int64_t n,
+                        int64_t counts[4], double sums[3], int mem);
+
 #ifdef __cplusplus
 }
 #endif
