@@ -9,7 +9,8 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
 * :class:`RandomForestClassifier`, :func:`rforest_train`, :func:`rforest_predict`,
   :func:`poisson_bag` -- train_clf=rf
 * :class:`NeuralNetworkClassifier`, :func:`nn_config_from`, :func:`nn_init_params`,
-  :func:`nn_train`, :func:`nn_predict`, :func:`nn_statistics` -- train_clf=nn
+  :func:`nn_train`, :func:`nn_train_opt`, :func:`nn_predict`, :func:`nn_statistics` --
+  train_clf=nn
   (the other classifiers live in :mod:`classification`; :func:`pipeline.run_train_clf` is the
   train/test flow over ``OffLineDataProvider.split`` with the rows resident on the device)
 * :mod:`brainvision` -- native .vhdr/.vmrk reader and marker planner
@@ -19,8 +20,8 @@ from .brainvision import (ChannelInfo, EEGMarker, Header, plan_markers, read_hea
                           read_markers, read_raw, recording_frames)
 from .classification import (DecisionTreeClassifier, NeuralNetworkClassifier,
                              RandomForestClassifier, dtree_predict, dtree_train, nn_config_from,
-                             nn_init_params, nn_predict, nn_statistics, nn_train, poisson_bag,
-                             rforest_predict, rforest_train)
+                             nn_init_params, nn_predict, nn_statistics, nn_train, nn_train_opt,
+                             poisson_bag, rforest_predict, rforest_train)
 from .context import Context, device_count
 from .data_provider import OffLineDataProvider
 from .feature_extraction import IFeatureExtraction, WaveletTransform
@@ -30,6 +31,6 @@ __all__ = [
     "IFeatureExtraction", "LIB_PATH", "NeuralNetworkClassifier", "OffLineDataProvider",
     "RandomForestClassifier", "WaveletTransform", "device_count", "dtree_predict", "dtree_train",
     "lib", "nn_config_from", "nn_init_params", "nn_predict", "nn_statistics", "nn_train",
-    "plan_markers", "poisson_bag", "read_header", "read_markers", "read_raw", "recording_frames",
+    "nn_train_opt", "plan_markers", "poisson_bag", "read_header", "read_markers", "read_raw", "recording_frames",
     "rforest_predict", "rforest_train",
 ]

@@ -94,6 +94,18 @@ class NnConfig(Structure):
                 ("num_iterations", c_int32), ("learning_rate", c_double), ("momentum", c_double)]
 
 
+NN_OPTIMIZERS = {"stochastic_gradient_descent": 0, "line_gradient_descent": 1,
+                 "conjugate_gradient": 2, "lbfgs": 3}
+
+
+class NnOptimizer(Structure):
+    _fields_ = [("algorithm", c_int32), ("max_line_search_iterations", c_int32)]
+
+
+class NnSearch(Structure):
+    _fields_ = [("step", c_double), ("score", c_double), ("trials", c_int32), ("pad", c_int32)]
+
+
 class EegfxError(RuntimeError):
     """A non-zero status of the C ABI (carries the code and eegfx_last_error())."""
 
@@ -217,6 +229,9 @@ SIGNATURES = {
     "eegfx_nn_param_count": (c_int64, [c_int32, POINTER(NnConfig)]),
     "eegfx_nn_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(NnConfig),
                                c_void_p, c_void_p, c_void_p, c_int]),
+    "eegfx_nn_train_opt": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                   POINTER(NnConfig), POINTER(NnOptimizer), c_void_p, c_void_p,
+                                   c_void_p, c_void_p, POINTER(c_int32), c_int]),
     "eegfx_nn_predict": (c_int, [c_void_p, c_void_p, c_int64, c_int32, POINTER(NnConfig), c_void_p,
                                  c_void_p, c_int]),
     "eegfx_nn_statistics": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

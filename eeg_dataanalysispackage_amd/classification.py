@@ -545,7 +545,8 @@ NN_WEIGHT_INITS = ("xavier", "zero", "sigmoid", "uniform", "relu")
 class NnModel:
     """A checked train_clf=nn model: d features, the layers' widths and activation names, the
     loss and updater names (unknown strings already mapped as the reference's parse* do), and the
-    training settings."""
+    training settings.  optimization_algo other than stochastic_gradient_descent trains through
+    eegfx_nn_train_opt with max_line_search_iterations trials a search."""
     d: int
     widths: Tuple[int, ...]
     activations: Tuple[str, ...]
@@ -556,6 +557,14 @@ class NnModel:
     num_iterations: int = 1000
     seed: int = 12345
     weight_init: str = "xavier"
+    optimization_algo: str = "stochastic_gradient_descent"
+    max_line_search_iterations: int = 5
+
+    def optimizer(self) -> "_lib.NnOptimizer":
+        o = _lib.NnOptimizer()
+        o.algorithm = _lib.NN_OPTIMIZERS[self.optimization_algo]
+        o.max_line_search_iterations = int(self.max_line_search_iterations)
+        return o
 
     def struct(self, num_iterations: Optional[int] = None) -> "_lib.NnConfig":
         c = _lib.NnConfig()
@@ -588,7 +597,10 @@ def _nn_refuse(code, key, value, why):
     raise EegfxError(code, f"{key}={value}: {why}")
 
 
-def nn_config_from(config: Dict[str, str], d: int) -> NnModel:
+NN_LINE_SEARCH_ALGOS = ("line_gradient_descent", "lbfgs", "conjugate_gradient")
+
+
+def nn_config_from(config: Dict[str, str], d: int, line_search: bool = False) -> NnModel:
     """The model NeuralNetworkClassifier.java:102-137, 258-320 builds from the config_* keys, or
     EegfxError naming the key and the value for what this library does not train.  Layer i = 1..L
     reads config_layer<i>_{layer_type, drop_out, activation_function, n_out}; L = the number of
@@ -596,8 +608,10 @@ def nn_config_from(config: Dict[str, str], d: int) -> NnModel:
     sigmoid, loss -> mse, updater -> nesterovs, weight init -> relu, optimization algorithm ->
     stochastic_gradient_descent, layer type -> output).  Refused: a missing key (the reference
     dies on null), auto_encoder / rbm / graves_lstm layers, a dense last layer or an output layer
-    that is not last, dropout, the line-search optimisers, pretrain=true, backprop other than
-    true, more than 4 layers, hidden widths outside [1, 64], an output width other than 2."""
+    that is not last, dropout, pretrain=true, backprop other than true, more than 4 layers, hidden
+    widths outside [1, 64], an output width other than 2 -- and, unless line_search is true, the
+    line-search optimisers (line_gradient_descent, conjugate_gradient, lbfgs): with it they become
+    NnModel.optimization_algo (DL4J's five line-search trials) and nn_train runs them."""
     def get(key):
         if key not in config or config[key] is None:
             raise EegfxError(_lib.EEGFX_EINVAL, f"{key} is missing (the reference dies on null)")
@@ -617,9 +631,9 @@ def nn_config_from(config: Dict[str, str], d: int) -> NnModel:
                          f"{n_layers} layers (the config_layer* keys // 4): 1 to "
                          f"{_lib.NN_MAX_LAYERS} are supported")
     algo = get("config_optimization_algo")
-    if algo in ("line_gradient_descent", "lbfgs", "conjugate_gradient"):
+    if algo in NN_LINE_SEARCH_ALGOS and not line_search:
         _nn_refuse(_lib.EEGFX_ENOTSUP, "config_optimization_algo", algo,
-                   "only stochastic_gradient_descent is trained")
+                   "a line-search optimiser: pass line_search=True to train under it")
     if get("config_pretrain") == "true":
         _nn_refuse(_lib.EEGFX_ENOTSUP, "config_pretrain", "true", "no layer here pretrains")
     if get("config_backprop") != "true":
@@ -665,7 +679,9 @@ def nn_config_from(config: Dict[str, str], d: int) -> NnModel:
                    learning_rate=number("config_learning_rate", float),
                    momentum=number("config_momentum", float), num_iterations=iterations,
                    seed=number("config_seed", int),
-                   weight_init=init if init in NN_WEIGHT_INITS else "relu")
+                   weight_init=init if init in NN_WEIGHT_INITS else "relu",
+                   optimization_algo=(algo if algo in NN_LINE_SEARCH_ALGOS
+                                      else "stochastic_gradient_descent"))
 
 
 def nn_init_params(model: NnModel) -> np.ndarray:
@@ -704,6 +720,16 @@ def nn_train(ctx: Context, X, y, model: NnModel, params0=None, num_iterations=No
     the trained flat vector and the loss before each iteration's step.  X (n x d float64) and y
     (n labels 0/1) are both host arrays or both device tensors; the results are host arrays
     (params_out / scores_out: caller's float64 buffers to fill instead of new ones)."""
+    if model.optimization_algo != "stochastic_gradient_descent":
+        return nn_train_opt(ctx, X, y, model, params0, num_iterations, params_out, scores_out)[:2]
+    X, y, n, d, mem, cfg, p0, out, scores = _nn_train_args(X, y, model, params0, num_iterations,
+                                                           params_out, scores_out)
+    ctx._call(mem, X, lib().eegfx_nn_train, ctx.handle, ptr(X), ptr(y), n, d, byref(cfg), ptr(p0),
+              ptr(out), ptr(scores), mem)
+    return out, scores
+
+
+def _nn_train_args(X, y, model, params0, num_iterations, params_out, scores_out):
     X, y, n, d, mem = _train_inputs(X, y)
     if d != model.d:
         raise ValueError(f"X has {d} features, the model {model.d}")
@@ -717,9 +743,38 @@ def nn_train(ctx: Context, X, y, model: NnModel, params0=None, num_iterations=No
            else _check_out(params_out, (count,)))
     scores = (np.empty(max(cfg.num_iterations, 0), dtype=np.float64) if scores_out is None
               else _check_out(scores_out, (max(cfg.num_iterations, 0),)))
-    ctx._call(mem, X, lib().eegfx_nn_train, ctx.handle, ptr(X), ptr(y), n, d, byref(cfg), ptr(p0),
-              ptr(out), ptr(scores), mem)
-    return out, scores
+    return X, y, n, d, mem, cfg, p0, out, scores
+
+
+NN_SEARCH_DTYPE = np.dtype([("step", np.float64), ("score", np.float64), ("trials", np.int32),
+                            ("pad", np.int32)])
+
+
+def nn_train_opt(ctx: Context, X, y, model: NnModel, params0=None, num_iterations=None,
+                 params_out=None, scores_out=None, search_out=None):
+    """nn_train under model.optimization_algo (eegfx_nn_train_opt):
+    returns (params, scores, search, iterations_run).  scores[i] is the loss at the start of
+    iteration i and search[i] (NN_SEARCH_DTYPE: step, score, trials) what its line search
+    returned; arrays made here end at iterations_run, a caller's scores_out / search_out
+    (num_iterations entries) keeps what it held from there on.  stochastic_gradient_descent is
+    eegfx_nn_train itself: iterations_run = num_iterations and search stays as it was."""
+    X, y, n, d, mem, cfg, p0, out, scores = _nn_train_args(X, y, model, params0, num_iterations,
+                                                           params_out, scores_out)
+    iters = max(cfg.num_iterations, 0)
+    if search_out is None:
+        search = np.zeros(iters, dtype=NN_SEARCH_DTYPE)
+    else:
+        search = search_out
+        if (not isinstance(search, np.ndarray) or search.dtype != NN_SEARCH_DTYPE
+                or search.shape != (iters,) or not search.flags.c_contiguous):
+            raise ValueError(f"search_out must be a contiguous NN_SEARCH_DTYPE array of {iters}")
+    opt = model.optimizer()
+    run = c_int32(0)
+    ctx._call(mem, X, lib().eegfx_nn_train_opt, ctx.handle, ptr(X), ptr(y), n, d, byref(cfg),
+              byref(opt), ptr(p0), ptr(out), ptr(scores), ptr(search), byref(run), mem)
+    done = int(run.value)
+    return (out, scores[:done] if scores_out is None else scores,
+            search[:done] if search_out is None else search, done)
 
 
 def nn_predict(ctx: Context, X, model: NnModel, params, out=None):
@@ -811,8 +866,8 @@ class NeuralNetworkClassifier(_Classifier):
     def trainFeatures(self, X, y) -> None:
         """:69-149 -- the network of the config_* keys (nn_config_from: every key is required, as
         in the reference), initialised by nn_init_params from config_seed and config_weight_init,
-        fitted by config_num_iterations full-batch iterations."""
-        self.model = nn_config_from(self.config, int(X.shape[1]))
+        fitted by config_num_iterations full-batch iterations under config_optimization_algo."""
+        self.model = nn_config_from(self.config, int(X.shape[1]), line_search=True)
         self.params, self.scores = nn_train(self.context, X, y, self.model)
 
     def _predict_rows(self, features):
@@ -839,6 +894,6 @@ class NeuralNetworkClassifier(_Classifier):
 __all__ = ["ClassificationStatistics", "DecisionTreeClassifier", "LogisticRegressionClassifier",
            "NeuralNetworkClassifier", "NnModel", "RandomForestClassifier", "SVMClassifier",
            "java_round", "nn_config_from", "nn_init_params", "nn_predict", "nn_statistics",
-           "nn_train", "reference_nn_statistics", "confusion_counts", "dtree_predict",
-           "dtree_train", "poisson_bag", "predict", "reference_statistics", "rforest_predict",
+           "nn_train", "nn_train_opt", "reference_nn_statistics", "confusion_counts",
+           "dtree_predict", "dtree_train", "poisson_bag", "predict", "reference_statistics", "rforest_predict",
            "rforest_train", "sgd_train", "spark_sample", "svm_predict", "svm_sgd_train", "EegfxError"]

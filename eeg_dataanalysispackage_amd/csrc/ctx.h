@@ -199,6 +199,8 @@ struct eegfx_ctx {
   // parameters), the gradient partials, the loss per iteration; eegfx_nn_statistics: a host
   // caller's scores (its labels go to row_vals), the counters followed by the partial sums.
   DevBuf nn_state, nn_part, nn_scores, nn_in, nn_stat;
+  // eegfx_nn_train_opt: NnOpt with the optimiser's vectors, one NnSearchRec per iteration
+  DevBuf nn_opt, nn_search;
   PinBuf pin_in, pin_out;                // small-batch extract_features staging (zero-copy)
   PinBuf pin_chunk[2];                   // streamed path: host staging of pageable recordings;
                                          // a sharded provider's worker: the file spans it reads
@@ -230,7 +232,8 @@ struct eegfx_ctx {
     return std::array{&raw, &pos, &out, &scratch, &fused, &rows_x, &row_vals, &lr_state, &lr_part,
                       &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_nodes,
                       &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
-                      &fl_flag, &nn_state, &nn_part, &nn_scores, &nn_in, &nn_stat};
+                      &fl_flag, &nn_state, &nn_part, &nn_scores, &nn_in, &nn_stat,
+                      &nn_opt, &nn_search};
   }
   void bind_buffers() {
     for (DevBuf* b : buffers()) b->sp = &stream;

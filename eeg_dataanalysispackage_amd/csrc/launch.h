@@ -302,6 +302,48 @@ hipError_t launch_nn_iteration(hipStream_t st, const double* X, const double* y,
                                double* partial, double lr, double momentum, double* scores);
 hipError_t launch_nn_predict(hipStream_t st, const double* X, int64_t n, const NnNet& net,
                              const NnTile& tl, const double* params, double* out);
+// The line-search optimisers of eegfx_nn_train_opt.  NnState::flag 1:
+// training has terminated (ZeroDirection / EpsTermination); every kernel then returns at once.
+constexpr int kNnLbfgsM = 4;       // LBFGS history
+constexpr int kNnOptVectors = 6;   // g, g_new, dir, cand, p_old, g_old ...
+constexpr int kNnOptVectorsLbfgs = kNnOptVectors + 2 * kNnLbfgsM;  // ... s[m], y[m]
+struct NnLine {                    // BackTrackLineSearch's state between two trials
+  double s0, slope, step_min;      // the score at p, -dot(dir, g), relTolx / test
+  double step, step2, sc, sc2;     // this trial's step and the one before, with their scores
+  double best, best_step;
+  int32_t trials;                  // trials evaluated in this search
+  int32_t done;                    // 1: the search of iteration `it` has ended
+};
+struct NnSearchRec {               // eegfx_nn_search
+  double step, score;
+  int32_t trials, pad;
+};
+struct NnOpt {       // followed by double [kNnOptVectors or kNnOptVectorsLbfgs][P]
+  NnLine line;
+  double score, score_new;         // the loss at p; what the last gradient pass reported
+  double rho[kNnLbfgsM];           // LBFGS ring: 1 / (dot(s, y) + EPS) per slot
+  int32_t it;                      // the iteration the search state belongs to
+  int32_t iterations_run;
+  int32_t hist, head;              // LBFGS: pairs held, slot of the newest
+  uint32_t ticket;                 // workgroups of the running nn_search_kernel that have finished
+  int32_t pad;
+};
+// The gradient pass of the optimisers: nn_grad_kernel, then nn_update_g_kernel (the updater's
+// output stored as g_new, the loss as NnOpt::score_new; NnState::iter counts the passes).
+hipError_t launch_nn_gradient_pass(hipStream_t st, const double* X, const double* y, int64_t n,
+                                   const NnNet& net, const NnTile& tl, int G, NnState* state,
+                                   NnOpt* opt, double* partial, double lr, double momentum);
+// One trial: nn_score_kernel (the loss of NnOpt's candidate, in the gradient launch's tiles, grid
+// and partial slots), then nn_search_kernel (the search's decision; search: one record per
+// iteration).  Both return at once when the iteration's search has ended.
+hipError_t launch_nn_trial(hipStream_t st, const double* X, const double* y, int64_t n,
+                           const NnNet& net, const NnTile& tl, int G, NnState* state, NnOpt* opt,
+                           double* partial, int max_ls, NnSearchRec* search);
+// nn_direction_kernel: the next direction (algorithm: EEGFX_NN_OPT_*), both termination tests,
+// scores[it + 1] and the set-up of the next search.  first: behind the gradient pass at params0.
+hipError_t launch_nn_direction(hipStream_t st, const NnNet& net, int algorithm, int iterations,
+                               bool first, NnState* state, NnOpt* opt, double* scores,
+                               NnSearchRec* search);
 struct NnStatsOut {                   // zeroed by the caller
   unsigned long long cell[4];         // tp, tn, fp, fn of ClassificationStatistics.add
 };

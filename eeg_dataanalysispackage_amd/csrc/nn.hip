@@ -19,6 +19,19 @@
 //                     updater's elementwise step; workgroup 0 also sums the losses into
 //                     scores[iteration].  The last workgroup to finish advances the iteration.
 // The order of every sum is a function of (n, d, the widths) alone: two runs give the same bits.
+// Under a line-search optimiser (eegfx_nn_train_opt) an iteration is the
+// fixed sequence maxLs x (nn_score_kernel, nn_search_kernel), nn_grad_kernel, nn_update_g_kernel,
+// nn_direction_kernel, still without a host round trip:
+//   nn_score_kernel   nn_grad_kernel's forward pass and row loss over a candidate vector, in the
+//                     same tiles, grid and loss slots: the bits the gradient pass would report.
+//   nn_search_kernel  one thread per parameter: every workgroup takes the same decision of the
+//                     backtracking line search from the state in device memory and writes its slice
+//                     of the next candidate or of the accepted parameters; the last one commits.
+//   nn_update_g_kernel  nn_update_kernel, but the updater's output is stored as the gradient the
+//                     optimisers see.
+//   nn_direction_kernel  one workgroup: the dot products, the CG / LBFGS direction, both
+//                     termination tests and the set-up of the next search, in an order fixed by P
+//                     alone.
 //   nn_predict_kernel the forward pass of nn_grad_kernel, output 0 of the last layer per row.
 //   nn_stats_kernel   ClassificationStatistics.add over (score, label) pairs: four integer
 //                     counters (atomics on integers), three sums as per-workgroup partials.
@@ -44,6 +57,7 @@ constexpr int kNnValidateMaxBlocks = 4096;
 constexpr int kNnStatThreads = 256;
 constexpr int kNnStatUnroll = 4;       // rows a thread takes per trip of nn_stats_kernel's loop
 constexpr int kNnStatMaxBlocks = 2048;
+constexpr int kNnDirThreads = 1024;   // the one workgroup of nn_direction_kernel
 
 namespace dev {
 
@@ -205,6 +219,45 @@ __device__ __forceinline__ double nn_term_sum(const double* lds, const NnTerm& t
   return acc;
 }
 
+// The loss of one row over the two outputs against {y0, y1}, and dL/dp of each: the one place
+// the gradient pass and the score pass (nn_score_kernel) take a row's loss from.
+__device__ __forceinline__ double nn_row_loss(int kind, double p0, double p1, double y0, double y1,
+                                              double* g0, double* g1) {
+  switch (kind) {
+    case EEGFX_NN_LOSS_XENT:
+      *g0 = -y0 / p0 + (1.0 - y0) / (1.0 - p0);
+      *g1 = -y1 / p1 + (1.0 - y1) / (1.0 - p1);
+      return -((y0 * log(p0) + (1.0 - y0) * log(1.0 - p0)) +
+               (y1 * log(p1) + (1.0 - y1) * log(1.0 - p1)));
+    case EEGFX_NN_LOSS_NLL:
+      *g0 = -y0 / p0;
+      *g1 = -y1 / p1;
+      return -(y0 * log(p0) + y1 * log(p1));
+    case EEGFX_NN_LOSS_SQUARED:
+      *g0 = 2.0 * (p0 - y0);
+      *g1 = 2.0 * (p1 - y1);
+      return (p0 - y0) * (p0 - y0) + (p1 - y1) * (p1 - y1);
+    default:
+      *g0 = p0 - y0;
+      *g1 = p1 - y1;
+      return ((p0 - y0) * (p0 - y0) + (p1 - y1) * (p1 - y1)) / 2.0;
+  }
+}
+
+// The workgroup's loss sum (row t of every tile in my_loss), in row order, into *out.
+__device__ __forceinline__ void nn_store_loss(const NnTile& tl, double* lds, double my_loss,
+                                              double* out) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  if (t < kNnMaxTileRows) lds[tl.loss_off + t] = my_loss;
+  __syncthreads();
+  if (t == 0) {
+    double s = 0.0;
+    for (int r = 0; r < kNnMaxTileRows; ++r) s += lds[tl.loss_off + r];
+    *out = s;
+  }
+}
+
 __global__ __launch_bounds__(kNnThreads) void nn_grad_kernel(
     const double* __restrict__ X, const double* __restrict__ y, int64_t n, const NnNet net,
     const NnTile tl, const NnState* __restrict__ st, double* __restrict__ partial) {
@@ -239,30 +292,8 @@ __global__ __launch_bounds__(kNnThreads) void nn_grad_kernel(
       double* z = lds + tl.z_off[last] + t * os;
       const double p0 = lds[tl.a_off[last] + t * os], p1 = lds[tl.a_off[last] + t * os + 1];
       const double y0 = lds[tl.y_off + t], y1 = fabs(1.0 - y0);  // labels[i] = {t, |1 - t|}
-      double loss, g0, g1;
-      switch (net.loss) {
-        case EEGFX_NN_LOSS_XENT:
-          loss = -((y0 * log(p0) + (1.0 - y0) * log(1.0 - p0)) +
-                   (y1 * log(p1) + (1.0 - y1) * log(1.0 - p1)));
-          g0 = -y0 / p0 + (1.0 - y0) / (1.0 - p0);
-          g1 = -y1 / p1 + (1.0 - y1) / (1.0 - p1);
-          break;
-        case EEGFX_NN_LOSS_NLL:
-          loss = -(y0 * log(p0) + y1 * log(p1));
-          g0 = -y0 / p0;
-          g1 = -y1 / p1;
-          break;
-        case EEGFX_NN_LOSS_SQUARED:
-          loss = (p0 - y0) * (p0 - y0) + (p1 - y1) * (p1 - y1);
-          g0 = 2.0 * (p0 - y0);
-          g1 = 2.0 * (p1 - y1);
-          break;
-        default:
-          loss = ((p0 - y0) * (p0 - y0) + (p1 - y1) * (p1 - y1)) / 2.0;
-          g0 = p0 - y0;
-          g1 = p1 - y1;
-          break;
-      }
+      double g0, g1;
+      const double loss = nn_row_loss(net.loss, p0, p1, y0, y1, &g0, &g1);
       my_loss += loss;
       double d0, d1;
       if ((net.loss == EEGFX_NN_LOSS_XENT && out_act == EEGFX_NN_ACT_SIGMOID) ||
@@ -323,13 +354,39 @@ __global__ __launch_bounds__(kNnThreads) void nn_grad_kernel(
 #pragma unroll
   for (int k = 0; k < kNnAccRegs; ++k)
     if (t + k * kNnThreads < P) slab[t + k * kNnThreads] = acc[k];
-  __syncthreads();
-  if (t < kNnMaxTileRows) lds[tl.loss_off + t] = my_loss;
-  __syncthreads();
-  if (t == 0) {
-    double s = 0.0;
-    for (int r = 0; r < kNnMaxTileRows; ++r) s += lds[tl.loss_off + r];
-    slab[P] = s;
+  nn_store_loss(tl, lds, my_loss, slab + P);
+}
+
+// The updater's u for the mean gradient g of one parameter (p <- p - u), iteration `it` (0-based),
+// its state advanced in place.
+__device__ __forceinline__ double nn_updater(int updater, double lr, double mu, int it, double g,
+                                             double* s1, double* s2) {
+  switch (updater) {
+    case EEGFX_NN_UPD_SGD:
+      return lr * g;
+    case EEGFX_NN_UPD_ADAM: {
+      const double b1 = 0.9, b2 = 0.999, t = (double)(it + 1);
+      const double m = b1 * *s1 + (1.0 - b1) * g;
+      const double v = b2 * *s2 + (1.0 - b2) * (g * g);
+      *s1 = m;
+      *s2 = v;
+      return lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t)) * (m / (sqrt(v) + 1e-8));
+    }
+    case EEGFX_NN_UPD_ADAGRAD: {
+      const double h = *s1 + g * g;
+      *s1 = h;
+      return lr * g / (sqrt(h) + 1e-6);
+    }
+    case EEGFX_NN_UPD_RMSPROP: {
+      const double r = 0.95 * *s1 + 0.05 * (g * g);
+      *s1 = r;
+      return lr * g / sqrt(r + 1e-8);
+    }
+    default: {  // nesterovs
+      const double v = *s1, vn = mu * v - lr * g;
+      *s1 = vn;
+      return mu * v - (1.0 + mu) * vn;
+    }
   }
 }
 
@@ -347,39 +404,7 @@ __global__ __launch_bounds__(kNnThreads) void nn_update_kernel(
     double* w = (double*)(st + 1) + p;
     double* s1 = w + P;
     double* s2 = s1 + P;
-    double u;
-    switch (updater) {
-      case EEGFX_NN_UPD_SGD:
-        u = lr * g;
-        break;
-      case EEGFX_NN_UPD_ADAM: {
-        const double b1 = 0.9, b2 = 0.999, t = (double)(it + 1);
-        const double m = b1 * *s1 + (1.0 - b1) * g;
-        const double v = b2 * *s2 + (1.0 - b2) * (g * g);
-        *s1 = m;
-        *s2 = v;
-        u = lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t)) * (m / (sqrt(v) + 1e-8));
-        break;
-      }
-      case EEGFX_NN_UPD_ADAGRAD: {
-        const double h = *s1 + g * g;
-        *s1 = h;
-        u = lr * g / (sqrt(h) + 1e-6);
-        break;
-      }
-      case EEGFX_NN_UPD_RMSPROP: {
-        const double r = 0.95 * *s1 + 0.05 * (g * g);
-        *s1 = r;
-        u = lr * g / sqrt(r + 1e-8);
-        break;
-      }
-      default: {  // nesterovs
-        const double v = *s1, vn = mu * v - lr * g;
-        *s1 = vn;
-        u = mu * v - (1.0 + mu) * vn;
-        break;
-      }
-    }
+    const double u = nn_updater(updater, lr, mu, it, g, s1, s2);
     *w = *w - u;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && scores) {
@@ -393,6 +418,379 @@ __global__ __launch_bounds__(kNnThreads) void nn_update_kernel(
     if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {  // every workgroup has read st->iter
       st->ticket = 0;
       st->iter = it + 1;
+    }
+  }
+}
+
+// ---- the line-search optimisers (eegfx_nn_train_opt) --------------------
+enum { kVecG = 0, kVecGNew = 1, kVecDir = 2, kVecCand = 3, kVecPOld = 4, kVecGOld = 5,
+       kVecS = 6, kVecY = kVecS + kNnLbfgsM };
+__device__ __forceinline__ double* nn_opt_vec(const NnOpt* opt, int k, int P) {
+  return (double*)(opt + 1) + (int64_t)k * P;
+}
+// p - step * dir: the one expression a candidate and the accepted parameters are made with, so
+// the parameters a search accepts are the bits of the candidate it scored.
+__device__ __forceinline__ double nn_move(double p, double step, double d) { return p - step * d; }
+__device__ __forceinline__ bool nn_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// nn_grad_kernel's forward pass and row loss over NnOpt's candidate vector: the same tiles, grid
+// and loss slot of `partial`, so the score of a vector is what the gradient pass reports for it.
+__global__ __launch_bounds__(kNnThreads) void nn_score_kernel(
+    const double* __restrict__ X, const double* __restrict__ y, int64_t n, const NnNet net,
+    const NnTile tl, const NnState* __restrict__ st, const NnOpt* __restrict__ opt,
+    double* __restrict__ partial) {
+  if (st->flag || opt->line.done) return;
+  extern __shared__ __attribute__((aligned(16))) double nn_lds[];
+  double* lds = nn_lds;
+  const double* params = nn_opt_vec(opt, kVecCand, net.P);
+  const int t = threadIdx.x, last = net.L - 1;
+  nn_stage_weights(net, tl, lds, params);
+  double my_loss = 0.0;  // of row t of every tile
+  for (int64_t row0 = (int64_t)blockIdx.x * tl.rows; row0 < n;
+       row0 += (int64_t)gridDim.x * tl.rows) {
+    const int rows = (int)(n - row0 < tl.rows ? n - row0 : tl.rows);
+    __syncthreads();  // the previous tile's loss step has read the tile
+    nn_load_rows(net, tl, lds, X, y, row0, rows);
+    __syncthreads();
+    nn_forward(net, tl, lds, params, rows);
+    if (t < rows) {
+      const int os = tl.a_stride[last];
+      const double p0 = lds[tl.a_off[last] + t * os], p1 = lds[tl.a_off[last] + t * os + 1];
+      const double y0 = lds[tl.y_off + t], y1 = fabs(1.0 - y0);
+      double g0, g1;
+      my_loss += nn_row_loss(net.loss, p0, p1, y0, y1, &g0, &g1);
+    }
+  }
+  nn_store_loss(tl, lds, my_loss, partial + (int64_t)blockIdx.x * (net.P + 1) + net.P);
+}
+
+// nn_update_kernel for the optimisers: the same sums, the same updater on the same state, but u
+// goes to g_new and the parameters stay; st->iter counts the gradient passes.
+__global__ __launch_bounds__(kNnThreads) void nn_update_g_kernel(
+    const double* __restrict__ partial, int G, int64_t n, int P, int updater, double lr,
+    double mu, NnState* __restrict__ st, NnOpt* __restrict__ opt) {
+  if (st->flag) return;
+  const int it = st->iter;  // every thread reads it before its workgroup takes a ticket
+  const int p = blockIdx.x * kNnThreads + threadIdx.x;
+  const int64_t stride = P + 1;
+  if (p < P) {
+    double g = 0.0;
+    for (int b = 0; b < G; ++b) g += partial[b * stride + p];
+    g = g / (double)n;
+    double* s1 = (double*)(st + 1) + P + p;
+    double* s2 = s1 + P;
+    nn_opt_vec(opt, kVecGNew, P)[p] = nn_updater(updater, lr, mu, it, g, s1, s2);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double s = 0.0;
+    for (int b = 0; b < G; ++b) s += partial[b * stride + P];
+    opt->score_new = s / (double)n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
+      st->ticket = 0;
+      st->iter = it + 1;
+    }
+  }
+}
+
+// One trial of BackTrackLineSearch with the trial's score `sc` at hand.  Returns what the
+// parameter threads do: 0 write the next candidate p - *move * dir, 1 the search has ended and
+// p <- p - *move * dir, 2 it has ended with step 0.  rec: the iteration's record once it ends.
+__device__ __forceinline__ int nn_line_step(NnLine& ln, double sc, int max_ls, double* move,
+                                            NnSearchRec* rec) {
+  const double s0 = ln.s0, slope = ln.slope, step = ln.step, prev = ln.sc;
+  ln.sc = sc;
+  ln.trials += 1;
+  rec->trials = ln.trials;
+  rec->pad = 0;
+  if (sc < ln.best) {
+    ln.best = sc;
+    ln.best_step = step;
+  }
+  if (sc <= s0 + 1e-4 * step * slope) {  // Armijo (false for a NaN score)
+    ln.done = 1;
+    rec->step = *move = step;
+    rec->score = sc;
+    return 1;
+  }
+  double tmp;
+  if (!nn_finite(sc) || !nn_finite(prev)) {
+    tmp = 0.2 * step;
+  } else if (step == 1.0) {
+    tmp = -slope / (2.0 * (sc - s0 - slope));
+  } else {
+    const double step2 = ln.step2;
+    const double r1 = sc - s0 - step * slope, r2 = ln.sc2 - s0 - step2 * slope;
+    const double q1 = r1 / (step * step), q2 = r2 / (step2 * step2);
+    const double a = (q1 - q2) / (step - step2);
+    const double b = (-step2 * q1 + step * q2) / (step - step2);
+    if (a == 0.0) {
+      tmp = -slope / (2.0 * b);
+    } else {
+      const double disc = b * b - 3.0 * a * slope;
+      if (disc < 0.0)
+        tmp = 0.5 * step;
+      else if (b <= 0.0)
+        tmp = (-b + sqrt(disc)) / (3.0 * a);
+      else
+        tmp = -slope / (b + sqrt(disc));
+    }
+    if (!(tmp < 0.5 * step)) tmp = 0.5 * step;
+  }
+  ln.step2 = step;
+  ln.sc2 = sc;
+  ln.step = tmp > 0.1 * step ? tmp : 0.1 * step;
+  if (ln.trials < max_ls && !(ln.step < ln.step_min)) {
+    *move = ln.step;
+    return 0;
+  }
+  ln.done = 1;
+  if (ln.trials == max_ls && ln.best < s0) {
+    rec->step = *move = ln.best_step;
+    rec->score = ln.best;
+    return 1;
+  }
+  rec->step = *move = 0.0;
+  rec->score = s0;
+  return 2;
+}
+
+// One thread per parameter.  Thread 0 of every workgroup sums the G loss partials in workgroup
+// order and takes the search's decision from the state in device memory (the same in every
+// workgroup); the workgroup then writes its slice of the next candidate or of the accepted p.  The
+// last workgroup to take a ticket commits the state: by then every workgroup has read it.
+__global__ __launch_bounds__(kNnThreads) void nn_search_kernel(
+    const double* __restrict__ partial, int G, int64_t n, int P, int max_ls,
+    NnState* __restrict__ st, NnOpt* __restrict__ opt, NnSearchRec* __restrict__ search) {
+  if (st->flag || opt->line.done) return;
+  __shared__ double sh_move;
+  __shared__ int sh_mode;
+  NnLine ln;
+  NnSearchRec rec;
+  int it = 0;
+  if (threadIdx.x == 0) {
+    ln = opt->line;
+    it = opt->it;
+    double s = 0.0;
+    for (int b = 0; b < G; ++b) s += partial[b * (int64_t)(P + 1) + P];
+    double move;
+    sh_mode = nn_line_step(ln, s / (double)n, max_ls, &move, &rec);
+    sh_move = move;
+  }
+  __syncthreads();
+  const int mode = sh_mode, k = blockIdx.x * kNnThreads + threadIdx.x;
+  if (k < P && mode != 2) {
+    double* p = (double*)(st + 1);
+    const double v = nn_move(p[k], sh_move, nn_opt_vec(opt, kVecDir, P)[k]);
+    if (mode == 1)
+      p[k] = v;
+    else
+      nn_opt_vec(opt, kVecCand, P)[k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(&opt->ticket, 1u) == gridDim.x - 1) {
+      opt->ticket = 0;
+      opt->line = ln;
+      if (ln.done) search[it] = rec;
+    }
+  }
+}
+
+// v[k] <- the workgroup's sum of v[k] over its kNnDirThreads threads, in a tree whose shape is
+// fixed; red: N * kNnDirThreads doubles of LDS.  Ends behind a barrier.
+template <int N>
+__device__ __forceinline__ void nn_block_sum(double (&v)[N], double* red) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < N; ++k) red[k * kNnDirThreads + t] = v[k];
+  __syncthreads();
+  for (int h = kNnDirThreads / 2; h > 0; h >>= 1) {
+    if (t < h) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) red[k * kNnDirThreads + t] += red[k * kNnDirThreads + t + h];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = red[k * kNnDirThreads];
+  __syncthreads();
+}
+// ... and the largest v; a NaN among them makes it a NaN, wherever it stands
+__device__ __forceinline__ double nn_block_max(double v, double* red) {
+  const int t = threadIdx.x;
+  red[t] = v;
+  __syncthreads();
+  for (int h = kNnDirThreads / 2; h > 0; h >>= 1) {
+    if (t < h && (red[t + h] > red[t] || red[t + h] != red[t + h])) red[t] = red[t + h];
+    __syncthreads();
+  }
+  v = red[0];
+  __syncthreads();
+  return v;
+}
+
+// One workgroup.  Thread t owns elements t, t + kNnDirThreads, ... of every vector (so no element
+// passes between threads but through the reductions), and sums them in that order: every sum's
+// order is a function of P alone.  After a gradient pass: the algorithm's next direction, g <-
+// g_new, ZeroDirection and EpsTermination (NnState::flag = 1), scores[it + 1], and the next
+// search's constants with its first candidate (or its return of 0 where 1 < stepMin).
+__global__ __launch_bounds__(kNnDirThreads) void nn_direction_kernel(
+    int P, int algo, int iters, int first, NnState* __restrict__ st, NnOpt* __restrict__ opt,
+    double* __restrict__ scores, NnSearchRec* __restrict__ search) {
+  if (st->flag) return;
+  __shared__ double red[3 * kNnDirThreads];
+  constexpr int D = kNnDirThreads, M = kNnLbfgsM;
+  const int t = threadIdx.x;
+  const double* p = (const double*)(st + 1);
+  double* g = nn_opt_vec(opt, kVecG, P);
+  const double* gn = nn_opt_vec(opt, kVecGNew, P);
+  double* dir = nn_opt_vec(opt, kVecDir, P);
+  double* p_old = nn_opt_vec(opt, kVecPOld, P);
+  double* g_old = nn_opt_vec(opt, kVecGOld, P);
+  // the scalars of the state, read by every thread before thread 0 writes any (at the end,
+  // behind the barriers of the reductions)
+  const int it = first ? -1 : opt->it;
+  const double old = opt->score, score = opt->score_new;
+  int hist = opt->hist, head = opt->head;
+  double rho_new = 0.0;
+  bool stop = false;
+  const bool lbfgs = algo == EEGFX_NN_OPT_LBFGS;
+  if (first) {
+    for (int k = t; k < P; k += D) {
+      const double v = gn[k];
+      g[k] = v;
+      dir[k] = v;
+      if (lbfgs) {
+        p_old[k] = p[k];
+        g_old[k] = v;
+      }
+    }
+  } else {
+    if (algo == EEGFX_NN_OPT_CG) {
+      double v[2] = {0.0, 0.0};  // dgg, gg
+      for (int k = t; k < P; k += D) {
+        v[0] += (gn[k] - g[k]) * gn[k];
+        v[1] += g[k] * g[k];
+      }
+      nn_block_sum(v, red);
+      const double q = v[0] / v[1], gamma = q < 0.0 ? 0.0 : q;
+      for (int k = t; k < P; k += D) dir[k] = gamma * dir[k] + gn[k];
+    } else if (lbfgs) {
+      head = hist == 0 ? 0 : (head + 1) % M;
+      hist = hist < M ? hist + 1 : M;
+      double* s_new = nn_opt_vec(opt, kVecS + head, P);
+      double* y_new = nn_opt_vec(opt, kVecY + head, P);
+      double v[2] = {0.0, 0.0};  // dot(s, y), dot(y, y)
+      for (int k = t; k < P; k += D) {
+        const double s = p[k] - p_old[k], yv = gn[k] - g_old[k];
+        s_new[k] = s;
+        y_new[k] = yv;
+        v[0] += s * yv;
+        v[1] += yv * yv;
+        dir[k] = gn[k];
+        p_old[k] = p[k];
+        g_old[k] = gn[k];
+      }
+      nn_block_sum(v, red);
+      const double sy = v[0] + 1e-5, yy = v[1] + 1e-5;
+      rho_new = 1.0 / sy;
+      double a[M];
+#pragma unroll
+      for (int j = 0; j < M; ++j) {  // newest -> oldest
+        a[j] = 0.0;
+        if (j < hist) {
+          const int slot = (head - j + M) % M;
+          const double* sv = nn_opt_vec(opt, kVecS + slot, P);
+          const double* yv = nn_opt_vec(opt, kVecY + slot, P);
+          double d[1] = {0.0};
+          for (int k = t; k < P; k += D) d[0] += sv[k] * dir[k];
+          nn_block_sum(d, red);
+          a[j] = (j == 0 ? rho_new : opt->rho[slot]) * d[0];
+          for (int k = t; k < P; k += D) dir[k] -= a[j] * yv[k];
+        }
+      }
+      const double scale = sy / yy;
+      for (int k = t; k < P; k += D) dir[k] *= scale;
+#pragma unroll
+      for (int j = M - 1; j >= 0; --j) {  // oldest -> newest
+        if (j < hist) {
+          const int slot = (head - j + M) % M;
+          const double* sv = nn_opt_vec(opt, kVecS + slot, P);
+          const double* yv = nn_opt_vec(opt, kVecY + slot, P);
+          double d[1] = {0.0};
+          for (int k = t; k < P; k += D) d[0] += yv[k] * dir[k];
+          nn_block_sum(d, red);
+          const double b = (j == 0 ? rho_new : opt->rho[slot]) * d[0];
+          for (int k = t; k < P; k += D) dir[k] += (a[j] - b) * sv[k];
+        }
+      }
+    } else {
+      for (int k = t; k < P; k += D) dir[k] = gn[k];
+    }
+    double asum[1] = {0.0};
+    for (int k = t; k < P; k += D) {
+      const double v = gn[k];
+      g[k] = v;
+      asum[0] += fabs(v);
+    }
+    nn_block_sum(asum, red);
+    stop = asum[0] == 0.0;  // ZeroDirection
+    if (!(score == 0.0 && old == 0.0) &&
+        2.0 * fabs(old - score) <= 1e-5 * (fabs(old) + fabs(score) + 1e-4))
+      stop = true;          // EpsTermination
+  }
+  const int next = it + 1;
+  const bool search_next = !stop && next < iters;
+  NnLine ln{};
+  if (search_next) {
+    double v[2] = {0.0, 0.0};  // dot(dir, dir), dot(dir, g)
+    double test = 0.0;
+    for (int k = t; k < P; k += D) {
+      v[0] += dir[k] * dir[k];
+      v[1] += dir[k] * g[k];
+      const double ap = fabs(p[k]), q = fabs(g[k]) / (ap > 1.0 ? ap : 1.0);
+      if (q > test || q != q) test = q;
+    }
+    nn_block_sum(v, red);
+    test = nn_block_max(test, red);
+    const double norm = sqrt(v[0]);
+    if (norm > 100.0) {  // stepMax; the slope stays what it was
+      const double f = 100.0 / norm;
+      for (int k = t; k < P; k += D) dir[k] *= f;
+    }
+    ln.s0 = ln.sc = ln.sc2 = ln.best = score;
+    ln.slope = -v[1];
+    ln.step_min = 1e-7 / test;
+    ln.step = ln.best_step = 1.0;
+    ln.step2 = 0.0;
+    ln.done = ln.step < ln.step_min ? 1 : 0;
+    if (!ln.done) {
+      double* cand = nn_opt_vec(opt, kVecCand, P);
+      for (int k = t; k < P; k += D) cand[k] = nn_move(p[k], 1.0, dir[k]);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    opt->score = score;
+    if (!first) {
+      opt->iterations_run = next;
+      if (lbfgs) {
+        opt->hist = hist;
+        opt->head = head;
+        opt->rho[head] = rho_new;
+      }
+    }
+    if (stop) st->flag = 1;
+    if (search_next) {
+      opt->it = next;
+      opt->line = ln;
+      if (scores) scores[next] = score;
+      if (ln.done) search[next] = NnSearchRec{0.0, score, 0, 0};
     }
   }
 }
@@ -561,6 +959,44 @@ hipError_t launch_nn_iteration(hipStream_t st, const double* X, const double* y,
   hipLaunchKernelGGL(dev::nn_update_kernel, dim3((net.P + kNnThreads - 1) / kNnThreads),
                      dim3(kNnThreads), 0, st, partial, G, n, net.P, net.updater, lr, momentum,
                      state, scores);
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_gradient_pass(hipStream_t st, const double* X, const double* y, int64_t n,
+                                   const NnNet& net, const NnTile& tl, int G, NnState* state,
+                                   NnOpt* opt, double* partial, double lr, double momentum) {
+  hipError_t e = nn_allow_lds(dev::nn_grad_kernel);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dev::nn_grad_kernel, dim3(G), dim3(kNnThreads),
+                     sizeof(double) * (size_t)tl.doubles, st, X, y, n, net, tl, state, partial);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dev::nn_update_g_kernel, dim3((net.P + kNnThreads - 1) / kNnThreads),
+                     dim3(kNnThreads), 0, st, partial, G, n, net.P, net.updater, lr, momentum,
+                     state, opt);
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_trial(hipStream_t st, const double* X, const double* y, int64_t n,
+                           const NnNet& net, const NnTile& tl, int G, NnState* state, NnOpt* opt,
+                           double* partial, int max_ls, NnSearchRec* search) {
+  hipError_t e = nn_allow_lds(dev::nn_score_kernel);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dev::nn_score_kernel, dim3(G), dim3(kNnThreads),
+                     sizeof(double) * (size_t)tl.doubles, st, X, y, n, net, tl, state, opt,
+                     partial);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dev::nn_search_kernel, dim3((net.P + kNnThreads - 1) / kNnThreads),
+                     dim3(kNnThreads), 0, st, partial, G, n, net.P, max_ls, state, opt, search);
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_direction(hipStream_t st, const NnNet& net, int algorithm, int iterations,
+                               bool first, NnState* state, NnOpt* opt, double* scores,
+                               NnSearchRec* search) {
+  hipLaunchKernelGGL(dev::nn_direction_kernel, dim3(1), dim3(kNnDirThreads), 0, st, net.P,
+                     algorithm, iterations, first ? 1 : 0, state, opt, scores, search);
   return hipGetLastError();
 }
 

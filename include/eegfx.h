@@ -708,6 +708,26 @@ int64_t eegfx_nn_param_count(int32_t d, const eegfx_nn_config* cfg);
 int eegfx_nn_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
                    const eegfx_nn_config* cfg, const double* params0, double* params_out,
                    double* scores_out, int mem);
+/* eegfx_nn_train under one of DL4J 0.8's line-search optimisers (config_optimization_algo =
+ * line_gradient_descent, conjugate_gradient -- the reference's default -- or lbfgs), as DESIGN.md
+ * section 10.8 defines them: every iteration a BackTrackLineSearch of at most
+ * max_line_search_iterations trials (1..32; DL4J's default is 5) along the direction the
+ * algorithm builds from the updater's output for the mean gradient, then a gradient pass at the
+ * new parameters; training stops early at ZeroDirection or EpsTermination.  params_out: the
+ * parameters after the last iteration run.  scores_out (may be NULL): the loss at the start of
+ * each iteration run; search_out (may be NULL): per iteration run the step the search returned,
+ * the score it holds for that step and the trials it evaluated; entries at or past
+ * *iterations_run (may be NULL) are left as they were.  algorithm == EEGFX_NN_OPT_SGD is
+ * eegfx_nn_train bit for bit (iterations_run = num_iterations, search_out untouched).  Labels,
+ * non-finite features, the order of the sums and `mem` as for eegfx_nn_train; num_iterations == 0
+ * returns params0 without a launch.  The call synchronises once, at its end. */
+enum { EEGFX_NN_OPT_SGD = 0, EEGFX_NN_OPT_LINE_GD = 1, EEGFX_NN_OPT_CG = 2, EEGFX_NN_OPT_LBFGS = 3 };
+typedef struct { int32_t algorithm; int32_t max_line_search_iterations; } eegfx_nn_optimizer;
+typedef struct { double step; double score; int32_t trials; int32_t pad; } eegfx_nn_search;
+int eegfx_nn_train_opt(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                       const eegfx_nn_config* cfg, const eegfx_nn_optimizer* opt,
+                       const double* params0, double* params_out, double* scores_out,
+                       eegfx_nn_search* search_out, int32_t* iterations_run, int mem);
 int eegfx_nn_predict(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,
                      const eegfx_nn_config* cfg, const double* params, double* out, int mem);
 int eegfx_nn_statistics(eegfx_ctx* ctx, const double* scores, const double* labels, int64_t n,

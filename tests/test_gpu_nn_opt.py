@@ -1,0 +1,279 @@
+"""The line-search optimisers of train_clf=nn on the device (eegfx_nn_train_opt; DESIGN.md section
+10.8) against the long-double restatement (tests/nn_opt_reference.py): trials and iterations run
+exactly, parameters, scores and steps within 1e-9 relative, a search's score the bits of the next
+gradient pass's; runs bit-identical to each other, from host and device rows, after a larger call;
+EEGFX_NN_OPT_SGD against eegfx_nn_train; the refusals; and the train/test flow under the
+reference's documented defaults."""
+import math
+from ctypes import byref, c_int32
+
+import numpy as np
+import pytest
+import torch
+
+import eeg_dataanalysispackage_amd as fx
+from eeg_dataanalysispackage_amd import _lib, pipeline
+from eeg_dataanalysispackage_amd import classification as clf
+from eeg_dataanalysispackage_amd.classification import NN_SEARCH_DTYPE, nn_train_opt
+from conftest import DOD02, INFO_TRAIN
+import nn_cases
+import nn_opt_cases as cases
+import nn_opt_reference as opt
+import nn_reference as ref
+from test_nn_reference import readme_config
+
+pytestmark = pytest.mark.gpu
+REL = 1e-9
+BAD_LABELS_TEXT = "Input validation failed: labels must be 0.0 or 1.0"
+HOST, DEV = _lib.MEM_HOST, _lib.MEM_DEVICE
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = fx.Context(0)
+    yield c
+    c.close()
+
+
+def model_of(case, **kw):
+    args = dict(d=case["d"], widths=case["widths"], activations=case["activations"],
+                loss=case["loss"], updater=case["updater"], learning_rate=case["learning_rate"],
+                momentum=case["momentum"], num_iterations=case["iterations"],
+                optimization_algo=case["algorithm"], max_line_search_iterations=case["max_ls"])
+    args.update(kw)
+    return clf.NnModel(**args)
+
+
+def device(a):
+    return torch.from_numpy(np.array(a, copy=True)).cuda()  # the cases' arrays are read-only
+
+
+def rel(got, want):
+    """The relative distance over the finite entries; the others must be non-finite alike."""
+    got = np.asarray(got, dtype=np.longdouble)
+    want = np.asarray(want, dtype=np.longdouble)
+    finite = np.isfinite(want)
+    assert np.array_equal(np.isfinite(got), finite)
+    return float(np.linalg.norm(got[finite] - want[finite]) /
+                 max(np.linalg.norm(want[finite]), np.longdouble(1e-300)))
+
+
+def bits(*arrays):
+    return b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
+
+
+def train(ctx, name, side=lambda a: a, **kw):
+    X, y, p0 = cases.data(name)
+    return nn_train_opt(ctx, side(X), side(y), model_of(cases.CASES[name], **kw), p0)
+
+
+# ---- parity ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(cases.CASES))
+def test_parity_with_the_restatement(ctx, name):
+    want = cases.reference(name)
+    params, scores, search, run = train(ctx, name)
+    assert run == want["iterations_run"] == len(scores) == len(search)
+    assert search["trials"].tolist() == want["trials"].tolist()
+    for what, a, b in (("params", params, want["params"]), ("scores", scores, want["scores"]),
+                       ("steps", search["step"], want["steps"]),
+                       ("search scores", search["score"], want["search_scores"])):
+        e = rel(a, b)
+        print(f"{name} {what}: {e:.3e}")
+        assert e <= REL
+    # the score kernel reports what the gradient pass then reports for the accepted vector
+    for i in range(run - 1):
+        if search["step"][i] != 0.0:
+            assert bits(search["score"][i]) == bits(scores[i + 1]), i
+        else:
+            assert bits(search["score"][i]) == bits(scores[i]) == bits(scores[i + 1]), i
+    if cases.CASES[name]["last_row_only"]:
+        assert params[0] != cases.data(name)[2][0]  # moved through the second trip's row alone
+
+
+# ---- bits -----------------------------------------------------------------------------------------
+BIT_CASES = ["cg_adam", "lbfgs_lr30_nll", "line_xent_saturates", "lbfgs_wide_d", "lbfgs_P_74050",
+             "cg_nan_row", "lbfgs_n_65"]
+
+
+@pytest.mark.parametrize("name", BIT_CASES)
+def test_twice_and_host_against_device(ctx, name):
+    a, b, c = train(ctx, name), train(ctx, name), train(ctx, name, device)
+    assert bits(*a[:3]) == bits(*b[:3]) == bits(*c[:3]) and a[3] == b[3] == c[3]
+
+
+def test_a_small_call_after_a_large_one(ctx):
+    """The context's buffers keep what the large call left: the small call must not read it."""
+    train(ctx, "lbfgs_P_74050")
+    train(ctx, "lbfgs_lr30_nll")
+    got = train(ctx, "lbfgs_zero_direction"), train(ctx, "lbfgs_n_65"), train(ctx, "cg_tanh_lr10")
+    fresh = fx.Context(0)
+    try:
+        want = (train(fresh, "lbfgs_zero_direction"), train(fresh, "lbfgs_n_65"),
+                train(fresh, "cg_tanh_lr10"))
+    finally:
+        fresh.close()
+    for g, w in zip(got, want):
+        assert bits(*g[:3]) == bits(*w[:3]) and g[3] == w[3]
+
+
+def test_sgd_is_eegfx_nn_train(ctx):
+    name = "lbfgs_adam"  # its searches backtrack: the line-search result is not SGD's
+    case = cases.CASES[name]
+    X, y, p0 = cases.data(name)
+    m = model_of(case, optimization_algo="stochastic_gradient_descent")
+    want_p, want_s = clf.nn_train(ctx, X, y, m, p0)
+    search = np.full(case["iterations"], -7.25).astype(NN_SEARCH_DTYPE)
+    keep = search.copy()
+    p, s, got_search, run = nn_train_opt(ctx, X, y, m, p0, search_out=search)
+    assert bits(p, s) == bits(want_p, want_s) and run == case["iterations"]
+    assert got_search is search and bits(search) == bits(keep)
+    # nn_train routes a line-search model through the new entry and returns its first two results
+    lm = model_of(case)
+    a = clf.nn_train(ctx, X, y, lm, p0)
+    b = nn_train_opt(ctx, X, y, lm, p0)
+    assert bits(*a) == bits(*b[:2]) and bits(a[0]) != bits(want_p)
+
+
+def test_no_iterations_returns_params0(ctx):
+    X, y, p0 = cases.data("cg_sgd")
+    p, s, search, run = nn_train_opt(ctx, X, y, model_of(cases.CASES["cg_sgd"]), p0,
+                                         num_iterations=0)
+    assert bits(p) == bits(p0) and s.shape == (0,) and search.shape == (0,) and run == 0
+
+
+def test_entries_past_iterations_run_are_left(ctx):
+    name = "lbfgs_zero_direction"  # 3 iterations asked, 1 run
+    case = cases.CASES[name]
+    X, y, p0 = cases.data(name)
+    scores = np.full(3, -7.25)
+    search = np.full(3, -7.25).astype(NN_SEARCH_DTYPE)
+    keep = search.copy()
+    _, s, r, run = nn_train_opt(ctx, X, y, model_of(case), p0, scores_out=scores,
+                                    search_out=search)
+    assert run == 1 and s is scores and r is search
+    assert scores[0] == 0.25 and (scores[1:] == -7.25).all()   # mse of p = 1/2 on both outputs
+    assert bits(search[1:]) == bits(keep[1:])
+    assert (search["step"][0], search["score"][0], search["trials"][0]) == (0.0, 0.25, 0)
+
+
+# ---- refusals -------------------------------------------------------------------------------------
+def test_refusals_name_field_and_value(ctx):
+    name = "cg_sgd"
+    X, y, p0 = cases.data(name)
+    m = model_of(cases.CASES[name])
+    cfg = m.struct()
+    out = np.full(p0.size, -7.25)
+    run = c_int32(-7)
+
+    def call(o, c=cfg, n=203, d=48):
+        return fx.lib().eegfx_nn_train_opt(ctx.handle, _lib.ptr(X), _lib.ptr(y), n, d, byref(c),
+                                           byref(o) if o is not None else None, _lib.ptr(p0),
+                                           _lib.ptr(out), None, None, byref(run), HOST)
+
+    for algorithm in (-1, 4, 7):
+        o = m.optimizer()
+        o.algorithm = algorithm
+        assert call(o) == _lib.EEGFX_EINVAL
+        assert f"algorithm={algorithm}".encode() in fx.lib().eegfx_last_error()
+    for trials in (0, -1, 33):
+        for algorithm in (0, 2):  # checked under SGD as well
+            o = m.optimizer()
+            o.algorithm, o.max_line_search_iterations = algorithm, trials
+            assert call(o) == _lib.EEGFX_EINVAL
+            assert f"max_line_search_iterations={trials}".encode() in fx.lib().eegfx_last_error()
+    assert call(None) == _lib.EEGFX_EINVAL
+    o = m.optimizer()
+    assert call(o, n=0) == _lib.EEGFX_EINVAL
+    assert call(o, d=1025) == _lib.EEGFX_EINVAL
+    bad = m.struct()
+    bad.n_out[1] = 3
+    assert call(o, bad) == _lib.EEGFX_EINVAL
+    assert b"config_layer2_n_out=3" in fx.lib().eegfx_last_error()
+    assert call(o, m.struct(-1)) == _lib.EEGFX_EINVAL
+    assert b"config_num_iterations=-1" in fx.lib().eegfx_last_error()
+    assert (out == -7.25).all() and run.value == -7
+    o.max_line_search_iterations = 32
+    assert call(o) == _lib.EEGFX_OK and run.value == 6  # every optional output may be NULL
+    want = nn_train_opt(ctx, X, y, model_of(cases.CASES[name], max_line_search_iterations=32),
+                            p0)
+    assert bits(out) == bits(want[0])
+
+
+VALIDATE_TRIP = (nn_cases.constants()["kNnValidateThreads"] *
+                 nn_cases.constants()["kNnValidateMaxBlocks"])
+
+
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_refused_label_in_the_second_trip(ctx, mem):
+    n = VALIDATE_TRIP + 1
+    m = clf.NnModel(d=1, widths=(1, 2), activations=("tanh", "softmax"),
+                    loss="negativeloglikelihood", num_iterations=2, optimization_algo="lbfgs")
+    p0 = clf.nn_init_params(m)
+    X = np.zeros((n, 1))
+    y = np.resize([0.0, 1.0, -0.0], n)
+    Xs, ys = (device(X), device(y)) if mem == DEV else (X, y)
+    assert nn_train_opt(ctx, Xs, ys, m, p0)[3] >= 1  # -0.0 passes
+    for bad in (0.5, math.nan):
+        ys[VALIDATE_TRIP] = bad
+        pout, sout = np.full(p0.size, -7.25), np.full(2, -7.25)
+        search = np.full(2, -7.25).astype(NN_SEARCH_DTYPE)
+        keep = search.copy()
+        with pytest.raises(fx.EegfxError) as e:
+            nn_train_opt(ctx, Xs, ys, m, p0, params_out=pout, scores_out=sout,
+                             search_out=search)
+        assert e.value.code == _lib.EEGFX_EINVAL and BAD_LABELS_TEXT in str(e.value)
+        assert (pout == -7.25).all() and (sout == -7.25).all() and bits(search) == bits(keep)
+
+
+# ---- the flow -------------------------------------------------------------------------------------
+def readme_defaults():
+    c = readme_config()
+    c["config_optimization_algo"] = "conjugate_gradient"  # the README's default
+    return c
+
+
+@pytest.mark.parametrize("args,epochs", [([INFO_TRAIN], 11), ([DOD02 + ".eeg", "4"], 27)],
+                         ids=["infoTrain", "DoD_2015_02"])
+def test_run_train_clf_under_the_readme_defaults(ctx, args, epochs):
+    from oracle import oracle
+    config = readme_defaults()
+    odp = fx.OffLineDataProvider(args, context=ctx)
+    try:
+        odp.loadData()
+        fe = fx.WaveletTransform(8, 512, 175, 16, context=ctx)
+        c = clf.NeuralNetworkClassifier(ctx)
+        c.setConfig(config)
+        stats = pipeline.run_train_clf(odp, c, fe)
+        assert c.model.optimization_algo == "conjugate_gradient"
+        data, labels = odp.getData(), odp.getDataLabels()
+        assert len(labels) == epochs
+        tr, te = pipeline.reference_split(len(labels))
+        assert stats.getNumberOfPatterns() == len(te)
+        h = clf.NeuralNetworkClassifier(ctx)  # the host route: train / test on epochs
+        h.setConfig(config)
+        h.train(data[tr], [labels[i] for i in tr], fe)
+        assert bits(h.params) == bits(c.params) and bits(h.scores) == bits(c.scores)
+        host_stats = h.test(data[te], [labels[i] for i in te])
+        assert host_stats.as_tuple() == stats.as_tuple()
+        for a, b in ((stats.MSE, host_stats.MSE), (stats.class1sum, host_stats.class1sum),
+                     (stats.class2sum, host_stats.class2sum)):
+            assert abs(a - b) <= REL * abs(b) or a == b
+        # the restatement on the oracle's features
+        ep, lab, _, err = oracle.data_provider(args)
+        assert not err and len(lab) == epochs
+        feats = oracle.extract_features(ep)
+        m = clf.nn_config_from(config, 48, line_search=True)
+        assert m == c.model
+        spec = dict(d=48, widths=m.widths, activations=m.activations, loss=m.loss,
+                    updater=m.updater, learning_rate=m.learning_rate, momentum=m.momentum)
+        want = opt.train_opt(clf.nn_init_params(m), feats[tr], np.array(lab)[tr], spec,
+                             m.optimization_algo, m.num_iterations, m.max_line_search_iterations)
+        m_, tag = opt.smallest_margin(want["trace"])
+        print(f"{want['iterations_run']} iterations run; closest decision {m_:.3e} at {tag}")
+        assert len(c.scores) == want["iterations_run"]
+        assert rel(c.params, want["params"]) <= REL and rel(c.scores, want["scores"]) <= REL
+        want_stats = clf.reference_nn_statistics(
+            ref.predict(want["params"], feats[te], spec), np.array(lab)[te])
+        assert stats.as_tuple() == want_stats.as_tuple()
+    finally:
+        odp.close()
