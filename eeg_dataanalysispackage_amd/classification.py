@@ -325,21 +325,27 @@ def reference_statistics(predictions, labels) -> ClassificationStatistics:
     return ClassificationStatistics(tp, tn, fp, fn)
 
 
+def _pair_inputs(values, labels, what):
+    """A (values, labels) pair for a device count: both host or both device, contiguous float64,
+    both [n].  Returns (values, labels, n, mem)."""
+    if _is_device(values) != _is_device(labels):
+        raise ValueError(f"{what} and labels must both be host or both be device arrays")
+    v = _contig(values, np.float64)
+    a = _contig(labels, np.float64)
+    n = int(v.shape[0])
+    if v.ndim != 1 or a.ndim != 1 or int(a.shape[0]) != n:
+        raise ValueError(f"{what} and labels must be [n], got {tuple(v.shape)} and "
+                         f"{tuple(a.shape)}")
+    return v, a, n, _mem(v, a)
+
+
 def confusion_counts(ctx: Context, predictions, labels):
     """(tp, tn, fp, fn) as reference_statistics reads them, counted on the device in one pass
     (eegfx_confusion_counts): only the four integers come back.  predictions and labels are both
     host arrays or both device tensors.  Raises IndexError where reference_statistics does (one
     actual class, or no rows) and EegfxError for a label that is neither 0.0 nor 1.0."""
-    if _is_device(predictions) != _is_device(labels):
-        raise ValueError("predictions and labels must both be host or both be device arrays")
-    p = _contig(predictions, np.float64)
-    a = _contig(labels, np.float64)
-    n = int(p.shape[0])
-    if p.ndim != 1 or a.ndim != 1 or int(a.shape[0]) != n:
-        raise ValueError(f"predictions and labels must be [n], got {tuple(p.shape)} and "
-                         f"{tuple(a.shape)}")
+    p, a, n, mem = _pair_inputs(predictions, labels, "predictions")
     counts = np.zeros(4, dtype=np.int64)
-    mem = _mem(p, a)
     ctx._call(mem, p, lib().eegfx_confusion_counts, ctx.handle, ptr(p), ptr(a), n, ptr(counts),
               mem)
     return tuple(int(v) for v in counts)
@@ -388,22 +394,33 @@ class _Classifier:
             raise RuntimeError("The classifier has not been trained")  # IllegalStateException
         return self._predict_rows(features)
 
+    # The two hooks of test / testFeatures: the reference's statistics of host predictions, and
+    # the same statistics counted on the device.
+    def _host_statistics(self, predictions, labels) -> ClassificationStatistics:
+        return reference_statistics(predictions, labels)
+
+    def _device_statistics(self, predictions, labels) -> ClassificationStatistics:
+        return ClassificationStatistics(*confusion_counts(self.context, predictions, labels))
+
     def test(self, epochs, targets: Sequence[float]) -> ClassificationStatistics:
+        """The statistics of the epochs' predictions (the network: NeuralNetworkClassifier.java
+        :152-168 -- resultsStats.add(output, target) per epoch)."""
         if not self._trained():
             raise RuntimeError("The classifier has not been trained")
-        return reference_statistics(self.predict(self._features(epochs)), targets)
+        return self._host_statistics(self.predict(self._features(epochs)), targets)
 
     def testFeatures(self, X, y) -> ClassificationStatistics:
         """test() on feature rows that exist already.  Predictions of device rows stay on the
-        device and are counted there (confusion_counts: four integers come back); host rows go
-        through reference_statistics as test() does."""
+        device and are counted there (confusion_counts: four integers come back; the network's
+        scores: nn_statistics); host rows go through reference_statistics (the network's:
+        reference_nn_statistics) as test() does."""
         pred = self.predict(X)
         if not _is_device(pred):
-            return reference_statistics(pred, y)
+            return self._host_statistics(pred, y)
         if not _is_device(y):
             import torch
             y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float64), device=pred.device)
-        return ClassificationStatistics(*confusion_counts(self.context, pred, y))
+        return self._device_statistics(pred, y)
 
 
 class LogisticRegressionClassifier(_Classifier):
@@ -832,17 +849,9 @@ def nn_statistics(ctx: Context, scores, labels) -> ClassificationStatistics:
     """reference_nn_statistics counted on the device in one pass (eegfx_nn_statistics): the four
     counters are exact, the three sums are added in the kernel's fixed order.  scores and labels
     are both host arrays or both device tensors."""
-    if _is_device(scores) != _is_device(labels):
-        raise ValueError("scores and labels must both be host or both be device arrays")
-    s = _contig(scores, np.float64)
-    a = _contig(labels, np.float64)
-    n = int(s.shape[0])
-    if s.ndim != 1 or a.ndim != 1 or int(a.shape[0]) != n:
-        raise ValueError(f"scores and labels must be [n], got {tuple(s.shape)} and "
-                         f"{tuple(a.shape)}")
+    s, a, n, mem = _pair_inputs(scores, labels, "scores")
     counts = np.zeros(4, dtype=np.int64)
     sums = np.zeros(3, dtype=np.float64)
-    mem = _mem(s, a)
     ctx._call(mem, s, lib().eegfx_nn_statistics, ctx.handle, ptr(s), ptr(a), n, ptr(counts),
               ptr(sums), mem)
     return ClassificationStatistics(*(int(v) for v in counts), MSE=float(sums[0]),
@@ -873,22 +882,11 @@ class NeuralNetworkClassifier(_Classifier):
     def _predict_rows(self, features):
         return nn_predict(self.context, features, self.model, self.params)
 
-    def test(self, epochs, targets: Sequence[float]) -> ClassificationStatistics:
-        """:152-168 -- resultsStats.add(output, target) per epoch."""
-        if not self._trained():
-            raise RuntimeError("The classifier has not been trained")
-        return reference_nn_statistics(self.predict(self._features(epochs)), targets)
+    def _host_statistics(self, scores, labels) -> ClassificationStatistics:
+        return reference_nn_statistics(scores, labels)
 
-    def testFeatures(self, X, y) -> ClassificationStatistics:
-        """test() on feature rows that exist already: the scores of device rows stay on the device
-        and are counted there (nn_statistics); host rows go through reference_nn_statistics."""
-        scores = self.predict(X)
-        if not _is_device(scores):
-            return reference_nn_statistics(scores, y)
-        if not _is_device(y):
-            import torch
-            y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float64), device=scores.device)
-        return nn_statistics(self.context, scores, y)
+    def _device_statistics(self, scores, labels) -> ClassificationStatistics:
+        return nn_statistics(self.context, scores, labels)
 
 
 __all__ = ["ClassificationStatistics", "DecisionTreeClassifier", "LogisticRegressionClassifier",

@@ -288,18 +288,13 @@ struct NnTile {
 struct NnState {     // followed by double params[P], s1[P], s2[P] (the updater's state)
   int32_t iter;      // iterations done
   int32_t flag;      // 2: label validation failed (every kernel then returns at once)
-  uint32_t ticket;   // workgroups of the running nn_update_kernel that have finished
+  uint32_t ticket;   // nn_last_workgroup's count for the running nn_update_kernel
   int32_t pad;
 };
 inline double* nn_params(NnState* st) { return (double*)(st + 1); }
 NnTile nn_plan_tile(const NnNet& net);
 int nn_grid(int64_t n, const NnNet& net, const NnTile& tl);
 hipError_t launch_nn_validate(hipStream_t st, const double* y, int64_t n, NnState* state);
-// one iteration: nn_grad_kernel, then nn_update_kernel.  partial: double [G][P + 1] (the
-// workgroup's gradient sums, then its loss sum); scores: null or one loss per iteration
-hipError_t launch_nn_iteration(hipStream_t st, const double* X, const double* y, int64_t n,
-                               const NnNet& net, const NnTile& tl, int G, NnState* state,
-                               double* partial, double lr, double momentum, double* scores);
 hipError_t launch_nn_predict(hipStream_t st, const double* X, int64_t n, const NnNet& net,
                              const NnTile& tl, const double* params, double* out);
 // The line-search optimisers of eegfx_nn_train_opt.  NnState::flag 1:
@@ -325,14 +320,17 @@ struct NnOpt {       // followed by double [kNnOptVectors or kNnOptVectorsLbfgs]
   int32_t it;                      // the iteration the search state belongs to
   int32_t iterations_run;
   int32_t hist, head;              // LBFGS: pairs held, slot of the newest
-  uint32_t ticket;                 // workgroups of the running nn_search_kernel that have finished
+  uint32_t ticket;                 // nn_last_workgroup's count for the running nn_search_kernel
   int32_t pad;
 };
-// The gradient pass of the optimisers: nn_grad_kernel, then nn_update_g_kernel (the updater's
-// output stored as g_new, the loss as NnOpt::score_new; NnState::iter counts the passes).
-hipError_t launch_nn_gradient_pass(hipStream_t st, const double* X, const double* y, int64_t n,
-                                   const NnNet& net, const NnTile& tl, int G, NnState* state,
-                                   NnOpt* opt, double* partial, double lr, double momentum);
+// nn_grad_kernel, then nn_update_kernel.  partial: double [G][P + 1] (the workgroup's gradient
+// sums, then its loss sum).  opt null: an SGD step (nn_update_kernel<false>; scores: null or one
+// loss per iteration).  opt set: the gradient pass of the optimisers (nn_update_kernel<true>: the
+// updater's output stored as g_new, the loss as NnOpt::score_new; NnState::iter counts the passes).
+hipError_t launch_nn_gradient(hipStream_t st, const double* X, const double* y, int64_t n,
+                              const NnNet& net, const NnTile& tl, int G, NnState* state,
+                              double* partial, double lr, double momentum, NnOpt* opt,
+                              double* scores);
 // One trial: nn_score_kernel (the loss of NnOpt's candidate, in the gradient launch's tiles, grid
 // and partial slots), then nn_search_kernel (the search's decision; search: one record per
 // iteration).  Both return at once when the iteration's search has ended.

@@ -48,6 +48,100 @@ NnNet nn_check_model(int32_t d, const eegfx_nn_config* cfg) {
   return net;
 }
 
+// The one training driver, inside the caller's `guarded`.  opt null or algorithm SGD: the
+// reference's plain loop of updater steps (search_out is never written, every iteration runs).
+// Otherwise one of the line-search optimisers; opt's own fields have been checked by the caller.
+void nn_train_impl(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, int32_t d,
+                   const eegfx_nn_config* cfg, const eegfx_nn_optimizer* opt,
+                   const double* params0, double* params_out, double* scores_out,
+                   eegfx_nn_search* search_out, int32_t* iterations_run, int mem) {
+  static_assert(sizeof(NnSearchRec) == sizeof(eegfx_nn_search), "eegfx_nn_search's layout");
+  if (!ctx || !cfg || !params0 || !params_out) fail(EEGFX_EINVAL, "null argument");
+  check_mem(mem);
+  if (n < 1) fail(EEGFX_EINVAL, "empty training set");
+  if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
+  const NnNet net = nn_check_model(d, cfg);
+  const int iters = cfg->num_iterations;
+  if (iters < 0) fail(EEGFX_EINVAL, "config_num_iterations=%d", iters);
+  const bool sgd = !opt || opt->algorithm == EEGFX_NN_OPT_SGD;
+  const size_t P = (size_t)net.P;
+  if (!sgd && iters == 0) {  // no device work: the labels are not validated (the SGD loop does)
+    memmove(params_out, params0, sizeof(double) * P);
+    if (iterations_run) *iterations_run = 0;
+    return;
+  }
+  ctx->activate();
+  const TrainXY rows = stage_xy(ctx, X, y, n, d, mem);
+  const size_t head = sizeof(NnState) + sizeof(double) * P;  // the state and the parameters
+  const size_t sbytes = head + 2 * sizeof(double) * P;       // ... and the updater's state
+  std::vector<uint8_t> hs(sbytes, 0);
+  NnState* h = (NnState*)hs.data();
+  memcpy(nn_params(h), params0, sizeof(double) * P);
+  NnState* st = (NnState*)ctx->nn_state.get(sbytes);
+  HIP_CHECK(hipMemcpyAsync(st, hs.data(), sbytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(launch_nn_validate(ctx->stream, rows.y, n, st));
+  const NnTile tl = nn_plan_tile(net);
+  const int G = nn_grid(n, net, tl);
+  double *part = nullptr, *dscores = nullptr;
+  if (iters > 0) {
+    part = (double*)ctx->nn_part.get(sizeof(double) * (size_t)G * (P + 1));
+    if (!sgd || scores_out) dscores = (double*)ctx->nn_scores.get(sizeof(double) * (size_t)iters);
+  }
+  const int64_t pass_bytes = n * (int64_t)sizeof(double) * (d + 1);
+  NnOpt* dopt = nullptr;
+  NnSearchRec* dsearch = nullptr;
+  if (sgd) {
+    for (int i = 0; i < iters; ++i) {
+      ctx->tic();
+      HIP_CHECK(launch_nn_gradient(ctx->stream, rows.X, rows.y, n, net, tl, G, st, part,
+                                   cfg->learning_rate, cfg->momentum, nullptr, dscores));
+      ctx->toc(pass_bytes);
+    }
+  } else {
+    const int max_ls = opt->max_line_search_iterations;
+    const int vectors = opt->algorithm == EEGFX_NN_OPT_LBFGS ? kNnOptVectorsLbfgs : kNnOptVectors;
+    dopt = (NnOpt*)ctx->nn_opt.get(sizeof(NnOpt) + sizeof(double) * P * (size_t)vectors);
+    HIP_CHECK(hipMemsetAsync(dopt, 0, sizeof(NnOpt), ctx->stream));
+    dsearch = (NnSearchRec*)ctx->nn_search.get(sizeof(NnSearchRec) * (size_t)iters);
+    // The fixed worst-case sequence: the kernels of a search that has ended, or of a training
+    // that has terminated, return at once, so nothing is read back before the end.
+    auto gradient_and_direction = [&](bool first) {
+      HIP_CHECK(launch_nn_gradient(ctx->stream, rows.X, rows.y, n, net, tl, G, st, part,
+                                   cfg->learning_rate, cfg->momentum, dopt, nullptr));
+      HIP_CHECK(launch_nn_direction(ctx->stream, net, opt->algorithm, iters, first, st, dopt,
+                                    dscores, dsearch));
+    };
+    gradient_and_direction(true);
+    for (int i = 0; i < iters; ++i) {
+      ctx->tic();
+      for (int k = 0; k < max_ls; ++k)
+        HIP_CHECK(launch_nn_trial(ctx->stream, rows.X, rows.y, n, net, tl, G, st, dopt, part,
+                                  max_ls, dsearch));
+      gradient_and_direction(false);
+      ctx->toc(pass_bytes);
+    }
+  }
+  NnOpt hopt{};
+  std::vector<double> scores((size_t)(dscores ? iters : 0));
+  std::vector<NnSearchRec> search((size_t)(dsearch ? iters : 0));
+  HIP_CHECK(hipMemcpyAsync(hs.data(), st, head, hipMemcpyDeviceToHost, ctx->stream));
+  if (dopt)
+    HIP_CHECK(hipMemcpyAsync(&hopt, dopt, sizeof(hopt), hipMemcpyDeviceToHost, ctx->stream));
+  if (dscores)
+    HIP_CHECK(hipMemcpyAsync(scores.data(), dscores, sizeof(double) * scores.size(),
+                             hipMemcpyDeviceToHost, ctx->stream));
+  if (dsearch)
+    HIP_CHECK(hipMemcpyAsync(search.data(), dsearch, sizeof(NnSearchRec) * search.size(),
+                             hipMemcpyDeviceToHost, ctx->stream));
+  ctx->drain();
+  if (h->flag == 2) fail(EEGFX_EINVAL, "%s", kBadLabels);
+  const size_t run = sgd ? (size_t)iters : (size_t)hopt.iterations_run;
+  memcpy(params_out, nn_params(h), sizeof(double) * P);
+  if (scores_out && dscores) memcpy(scores_out, scores.data(), sizeof(double) * run);
+  if (search_out && dsearch) memcpy(search_out, search.data(), sizeof(NnSearchRec) * run);
+  if (iterations_run) *iterations_run = (int32_t)run;
+}
+
 }  // namespace
 
 extern "C" {
@@ -62,46 +156,8 @@ int eegfx_nn_train(eegfx_ctx* ctx, const double* X, const double* y, int64_t n, 
                    const eegfx_nn_config* cfg, const double* params0, double* params_out,
                    double* scores_out, int mem) {
   return guarded([&] {
-    if (!ctx || !cfg || !params0 || !params_out) fail(EEGFX_EINVAL, "null argument");
-    check_mem(mem);
-    if (n < 1) fail(EEGFX_EINVAL, "empty training set");
-    if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
-    const NnNet net = nn_check_model(d, cfg);
-    const int iters = cfg->num_iterations;
-    if (iters < 0) fail(EEGFX_EINVAL, "config_num_iterations=%d", iters);
-    ctx->activate();
-    const auto [dX, dy] = stage_xy(ctx, X, y, n, d, mem);
-    const size_t P = (size_t)net.P;
-    const size_t head = sizeof(NnState) + sizeof(double) * P;  // the state and the parameters
-    const size_t sbytes = head + 2 * sizeof(double) * P;       // ... and the updater's state
-    std::vector<uint8_t> hs(sbytes, 0);
-    NnState* h = (NnState*)hs.data();
-    memcpy(nn_params(h), params0, sizeof(double) * P);
-    NnState* st = (NnState*)ctx->nn_state.get(sbytes);
-    HIP_CHECK(hipMemcpyAsync(st, hs.data(), sbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(launch_nn_validate(ctx->stream, dy, n, st));
-    const NnTile tl = nn_plan_tile(net);
-    const int G = nn_grid(n, net, tl);
-    std::vector<double> scores((size_t)(scores_out ? iters : 0));
-    double* dscores = nullptr;
-    if (iters > 0) {
-      double* part = (double*)ctx->nn_part.get(sizeof(double) * (size_t)G * (P + 1));
-      if (scores_out) dscores = (double*)ctx->nn_scores.get(sizeof(double) * (size_t)iters);
-      for (int i = 0; i < iters; ++i) {
-        ctx->tic();
-        HIP_CHECK(launch_nn_iteration(ctx->stream, dX, dy, n, net, tl, G, st, part,
-                                      cfg->learning_rate, cfg->momentum, dscores));
-        ctx->toc(n * (int64_t)sizeof(double) * (d + 1));
-      }
-    }
-    HIP_CHECK(hipMemcpyAsync(hs.data(), st, head, hipMemcpyDeviceToHost, ctx->stream));
-    if (dscores)
-      HIP_CHECK(hipMemcpyAsync(scores.data(), dscores, sizeof(double) * scores.size(),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    ctx->drain();
-    if (h->flag == 2) fail(EEGFX_EINVAL, "%s", kBadLabels);
-    memcpy(params_out, nn_params(h), sizeof(double) * P);
-    if (dscores) memcpy(scores_out, scores.data(), sizeof(double) * scores.size());
+    nn_train_impl(ctx, X, y, n, d, cfg, nullptr, params0, params_out, scores_out, nullptr, nullptr,
+                  mem);
   });
 }
 
@@ -109,88 +165,15 @@ int eegfx_nn_train_opt(eegfx_ctx* ctx, const double* X, const double* y, int64_t
                        const eegfx_nn_config* cfg, const eegfx_nn_optimizer* opt,
                        const double* params0, double* params_out, double* scores_out,
                        eegfx_nn_search* search_out, int32_t* iterations_run, int mem) {
-  static_assert(sizeof(NnSearchRec) == sizeof(eegfx_nn_search), "eegfx_nn_search's layout");
-  int rc = guarded([&] {
+  return guarded([&] {
     if (!opt) fail(EEGFX_EINVAL, "null argument");
     if (opt->algorithm < EEGFX_NN_OPT_SGD || opt->algorithm > EEGFX_NN_OPT_LBFGS)
       fail(EEGFX_EINVAL, "algorithm=%d is no EEGFX_NN_OPT_*", opt->algorithm);
     if (opt->max_line_search_iterations < 1 || opt->max_line_search_iterations > 32)
       fail(EEGFX_EINVAL, "max_line_search_iterations=%d outside [1, 32]",
            opt->max_line_search_iterations);
-  });
-  if (rc != EEGFX_OK) return rc;
-  if (opt->algorithm == EEGFX_NN_OPT_SGD) {
-    rc = eegfx_nn_train(ctx, X, y, n, d, cfg, params0, params_out, scores_out, mem);
-    if (rc == EEGFX_OK && iterations_run) *iterations_run = cfg->num_iterations;
-    return rc;
-  }
-  return guarded([&] {
-    if (!ctx || !cfg || !params0 || !params_out) fail(EEGFX_EINVAL, "null argument");
-    check_mem(mem);
-    if (n < 1) fail(EEGFX_EINVAL, "empty training set");
-    if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
-    const NnNet net = nn_check_model(d, cfg);
-    const int iters = cfg->num_iterations, max_ls = opt->max_line_search_iterations;
-    if (iters < 0) fail(EEGFX_EINVAL, "config_num_iterations=%d", iters);
-    const size_t P = (size_t)net.P;
-    if (iters == 0) {
-      memmove(params_out, params0, sizeof(double) * P);
-      if (iterations_run) *iterations_run = 0;
-      return;
-    }
-    ctx->activate();
-    const TrainXY rows = stage_xy(ctx, X, y, n, d, mem);
-    const double *dX = rows.X, *dy = rows.y;
-    const size_t head = sizeof(NnState) + sizeof(double) * P;
-    const size_t sbytes = head + 2 * sizeof(double) * P;
-    std::vector<uint8_t> hs(sbytes, 0);
-    NnState* h = (NnState*)hs.data();
-    memcpy(nn_params(h), params0, sizeof(double) * P);
-    NnState* st = (NnState*)ctx->nn_state.get(sbytes);
-    HIP_CHECK(hipMemcpyAsync(st, hs.data(), sbytes, hipMemcpyHostToDevice, ctx->stream));
-    const int vectors = opt->algorithm == EEGFX_NN_OPT_LBFGS ? kNnOptVectorsLbfgs : kNnOptVectors;
-    NnOpt* dopt = (NnOpt*)ctx->nn_opt.get(sizeof(NnOpt) + sizeof(double) * P * (size_t)vectors);
-    HIP_CHECK(hipMemsetAsync(dopt, 0, sizeof(NnOpt), ctx->stream));
-    HIP_CHECK(launch_nn_validate(ctx->stream, dy, n, st));
-    const NnTile tl = nn_plan_tile(net);
-    const int G = nn_grid(n, net, tl);
-    double* part = (double*)ctx->nn_part.get(sizeof(double) * (size_t)G * (P + 1));
-    double* dscores = (double*)ctx->nn_scores.get(sizeof(double) * (size_t)iters);
-    NnSearchRec* dsearch =
-        (NnSearchRec*)ctx->nn_search.get(sizeof(NnSearchRec) * (size_t)iters);
-    // The fixed worst-case sequence: the kernels of a search that has ended, or of a training
-    // that has terminated, return at once, so nothing is read back before the end.
-    auto gradient_and_direction = [&](bool first) {
-      HIP_CHECK(launch_nn_gradient_pass(ctx->stream, dX, dy, n, net, tl, G, st, dopt, part,
-                                        cfg->learning_rate, cfg->momentum));
-      HIP_CHECK(launch_nn_direction(ctx->stream, net, opt->algorithm, iters, first, st, dopt,
-                                    dscores, dsearch));
-    };
-    gradient_and_direction(true);
-    for (int i = 0; i < iters; ++i) {
-      ctx->tic();
-      for (int k = 0; k < max_ls; ++k)
-        HIP_CHECK(launch_nn_trial(ctx->stream, dX, dy, n, net, tl, G, st, dopt, part, max_ls,
-                                  dsearch));
-      gradient_and_direction(false);
-      ctx->toc(n * (int64_t)sizeof(double) * (d + 1));
-    }
-    NnOpt hopt;
-    std::vector<double> scores((size_t)iters);
-    std::vector<NnSearchRec> search((size_t)iters);
-    HIP_CHECK(hipMemcpyAsync(hs.data(), st, head, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(&hopt, dopt, sizeof(hopt), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(scores.data(), dscores, sizeof(double) * scores.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(search.data(), dsearch, sizeof(NnSearchRec) * search.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-    ctx->drain();
-    if (h->flag == 2) fail(EEGFX_EINVAL, "%s", kBadLabels);
-    const size_t run = (size_t)hopt.iterations_run;
-    memcpy(params_out, nn_params(h), sizeof(double) * P);
-    if (scores_out) memcpy(scores_out, scores.data(), sizeof(double) * run);
-    if (search_out) memcpy(search_out, search.data(), sizeof(NnSearchRec) * run);
-    if (iterations_run) *iterations_run = (int32_t)run;
+    nn_train_impl(ctx, X, y, n, d, cfg, opt, params0, params_out, scores_out, search_out,
+                  iterations_run, mem);
   });
 }
 

@@ -15,20 +15,21 @@
 //                     registers, the rest in the workgroup's own slab of `partial` (same thread
 //                     every time: no atomics).  At the end the slab holds the workgroup's sums and
 //                     its loss sum.
-//   nn_update_kernel  one thread per parameter: the partials summed in workgroup order, / n, the
-//                     updater's elementwise step; workgroup 0 also sums the losses into
-//                     scores[iteration].  The last workgroup to finish advances the iteration.
+//   nn_update_kernel<false>  one thread per parameter: the partials summed in workgroup order
+//                     (nn_partial_mean), / n, the updater's elementwise step; workgroup 0 also sums
+//                     the losses into scores[iteration].  The last workgroup to finish
+//                     (nn_last_workgroup) advances the iteration.
 // The order of every sum is a function of (n, d, the widths) alone: two runs give the same bits.
 // Under a line-search optimiser (eegfx_nn_train_opt) an iteration is the
-// fixed sequence maxLs x (nn_score_kernel, nn_search_kernel), nn_grad_kernel, nn_update_g_kernel,
-// nn_direction_kernel, still without a host round trip:
+// fixed sequence maxLs x (nn_score_kernel, nn_search_kernel), nn_grad_kernel,
+// nn_update_kernel<true>, nn_direction_kernel, still without a host round trip:
 //   nn_score_kernel   nn_grad_kernel's forward pass and row loss over a candidate vector, in the
 //                     same tiles, grid and loss slots: the bits the gradient pass would report.
 //   nn_search_kernel  one thread per parameter: every workgroup takes the same decision of the
 //                     backtracking line search from the state in device memory and writes its slice
 //                     of the next candidate or of the accepted parameters; the last one commits.
-//   nn_update_g_kernel  nn_update_kernel, but the updater's output is stored as the gradient the
-//                     optimisers see.
+//   nn_update_kernel<true>  the same kernel body, but the updater's output is stored as the
+//                     gradient the optimisers see.
 //   nn_direction_kernel  one workgroup: the dot products, the CG / LBFGS direction, both
 //                     termination tests and the set-up of the next search, in an order fixed by P
 //                     alone.
@@ -390,44 +391,66 @@ __device__ __forceinline__ double nn_updater(int updater, double lr, double mu, 
   }
 }
 
-__global__ __launch_bounds__(kNnThreads) void nn_update_kernel(
-    const double* __restrict__ partial, int G, int64_t n, int P, int updater, double lr,
-    double mu, NnState* __restrict__ st, double* __restrict__ scores) {
-  if (st->flag) return;
-  const int it = st->iter;  // every thread reads it before its workgroup takes a ticket
-  const int p = blockIdx.x * kNnThreads + threadIdx.x;
-  const int64_t stride = P + 1;
-  if (p < P) {
-    double g = 0.0;
-    for (int b = 0; b < G; ++b) g += partial[b * stride + p];
-    g = g / (double)n;
-    double* w = (double*)(st + 1) + p;
-    double* s1 = w + P;
-    double* s2 = s1 + P;
-    const double u = nn_updater(updater, lr, mu, it, g, s1, s2);
-    *w = *w - u;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && scores) {
-    double s = 0.0;
-    for (int b = 0; b < G; ++b) s += partial[b * stride + P];
-    scores[it] = s / (double)n;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {  // every workgroup has read st->iter
-      st->ticket = 0;
-      st->iter = it + 1;
-    }
-  }
-}
-
-// ---- the line-search optimisers (eegfx_nn_train_opt; DESIGN.md section 10.8) --------------------
+// The vectors behind NnOpt (the line-search optimisers, below).
 enum { kVecG = 0, kVecGNew = 1, kVecDir = 2, kVecCand = 3, kVecPOld = 4, kVecGOld = 5,
        kVecS = 6, kVecY = kVecS + kNnLbfgsM };
 __device__ __forceinline__ double* nn_opt_vec(const NnOpt* opt, int k, int P) {
   return (double*)(opt + 1) + (int64_t)k * P;
 }
+
+// Column p of the G workgroups' partials, summed in workgroup order, / n: the mean gradient of
+// parameter p, or (p == P) the loss.
+__device__ __forceinline__ double nn_partial_mean(const double* __restrict__ partial, int G,
+                                                  int64_t n, int P, int p) {
+  const int64_t stride = P + 1;
+  double s = 0.0;
+  for (int b = 0; b < G; ++b) s += partial[b * stride + p];
+  return s / (double)n;
+}
+
+// True in thread 0 of the last workgroup of the grid to get here, with the ticket reset: every
+// workgroup has then read the state that this thread goes on to commit.
+__device__ __forceinline__ bool nn_last_workgroup(uint32_t* ticket) {
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  __threadfence();
+  if (atomicAdd(ticket, 1u) != gridDim.x - 1) return false;
+  *ticket = 0;
+  return true;
+}
+
+// One thread per parameter: the updater's u for the mean gradient.  OPT == false (an SGD step):
+// p <- p - u, and the loss goes to scores[it] where scores is set.  OPT == true (the gradient
+// pass of the optimisers): the same sums, the same updater on the same state, but u goes to g_new,
+// the loss to NnOpt::score_new and the parameters stay; st->iter then counts the gradient passes.
+template <bool OPT>
+__global__ __launch_bounds__(kNnThreads) void nn_update_kernel(
+    const double* __restrict__ partial, int G, int64_t n, int P, int updater, double lr,
+    double mu, NnState* __restrict__ st, NnOpt* __restrict__ opt, double* __restrict__ scores) {
+  if (st->flag) return;
+  const int it = st->iter;  // every thread reads it before its workgroup takes a ticket
+  const int p = blockIdx.x * kNnThreads + threadIdx.x;
+  if (p < P) {
+    const double g = nn_partial_mean(partial, G, n, P, p);
+    double* w = (double*)(st + 1) + p;
+    double* s1 = w + P;
+    double* s2 = s1 + P;
+    const double u = nn_updater(updater, lr, mu, it, g, s1, s2);
+    if constexpr (OPT)
+      nn_opt_vec(opt, kVecGNew, P)[p] = u;
+    else
+      *w = *w - u;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if constexpr (OPT)
+      opt->score_new = nn_partial_mean(partial, G, n, P, P);
+    else if (scores)
+      scores[it] = nn_partial_mean(partial, G, n, P, P);
+  }
+  if (nn_last_workgroup(&st->ticket)) st->iter = it + 1;
+}
+
+// ---- the line-search optimisers (eegfx_nn_train_opt; DESIGN.md section 10.8) --------------------
 // p - step * dir: the one expression a candidate and the accepted parameters are made with, so
 // the parameters a search accepts are the bits of the candidate it scored.
 __device__ __forceinline__ double nn_move(double p, double step, double d) { return p - step * d; }
@@ -462,38 +485,6 @@ __global__ __launch_bounds__(kNnThreads) void nn_score_kernel(
     }
   }
   nn_store_loss(tl, lds, my_loss, partial + (int64_t)blockIdx.x * (net.P + 1) + net.P);
-}
-
-// nn_update_kernel for the optimisers: the same sums, the same updater on the same state, but u
-// goes to g_new and the parameters stay; st->iter counts the gradient passes.
-__global__ __launch_bounds__(kNnThreads) void nn_update_g_kernel(
-    const double* __restrict__ partial, int G, int64_t n, int P, int updater, double lr,
-    double mu, NnState* __restrict__ st, NnOpt* __restrict__ opt) {
-  if (st->flag) return;
-  const int it = st->iter;  // every thread reads it before its workgroup takes a ticket
-  const int p = blockIdx.x * kNnThreads + threadIdx.x;
-  const int64_t stride = P + 1;
-  if (p < P) {
-    double g = 0.0;
-    for (int b = 0; b < G; ++b) g += partial[b * stride + p];
-    g = g / (double)n;
-    double* s1 = (double*)(st + 1) + P + p;
-    double* s2 = s1 + P;
-    nn_opt_vec(opt, kVecGNew, P)[p] = nn_updater(updater, lr, mu, it, g, s1, s2);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    double s = 0.0;
-    for (int b = 0; b < G; ++b) s += partial[b * stride + P];
-    opt->score_new = s / (double)n;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-      st->ticket = 0;
-      st->iter = it + 1;
-    }
-  }
 }
 
 // One trial of BackTrackLineSearch with the trial's score `sc` at hand.  Returns what the
@@ -574,10 +565,8 @@ __global__ __launch_bounds__(kNnThreads) void nn_search_kernel(
   if (threadIdx.x == 0) {
     ln = opt->line;
     it = opt->it;
-    double s = 0.0;
-    for (int b = 0; b < G; ++b) s += partial[b * (int64_t)(P + 1) + P];
     double move;
-    sh_mode = nn_line_step(ln, s / (double)n, max_ls, &move, &rec);
+    sh_mode = nn_line_step(ln, nn_partial_mean(partial, G, n, P, P), max_ls, &move, &rec);
     sh_move = move;
   }
   __syncthreads();
@@ -590,14 +579,9 @@ __global__ __launch_bounds__(kNnThreads) void nn_search_kernel(
     else
       nn_opt_vec(opt, kVecCand, P)[k] = v;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(&opt->ticket, 1u) == gridDim.x - 1) {
-      opt->ticket = 0;
-      opt->line = ln;
-      if (ln.done) search[it] = rec;
-    }
+  if (nn_last_workgroup(&opt->ticket)) {
+    opt->line = ln;
+    if (ln.done) search[it] = rec;
   }
 }
 
@@ -947,33 +931,21 @@ hipError_t launch_nn_validate(hipStream_t st, const double* y, int64_t n, NnStat
   return hipGetLastError();
 }
 
-hipError_t launch_nn_iteration(hipStream_t st, const double* X, const double* y, int64_t n,
-                               const NnNet& net, const NnTile& tl, int G, NnState* state,
-                               double* partial, double lr, double momentum, double* scores) {
-  hipError_t e = nn_allow_lds(dev::nn_grad_kernel);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(dev::nn_grad_kernel, dim3(G), dim3(kNnThreads),
-                     sizeof(double) * (size_t)tl.doubles, st, X, y, n, net, tl, state, partial);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(dev::nn_update_kernel, dim3((net.P + kNnThreads - 1) / kNnThreads),
-                     dim3(kNnThreads), 0, st, partial, G, n, net.P, net.updater, lr, momentum,
-                     state, scores);
-  return hipGetLastError();
-}
+static dim3 nn_param_grid(int P) { return dim3((P + kNnThreads - 1) / kNnThreads); }
 
-hipError_t launch_nn_gradient_pass(hipStream_t st, const double* X, const double* y, int64_t n,
-                                   const NnNet& net, const NnTile& tl, int G, NnState* state,
-                                   NnOpt* opt, double* partial, double lr, double momentum) {
+hipError_t launch_nn_gradient(hipStream_t st, const double* X, const double* y, int64_t n,
+                              const NnNet& net, const NnTile& tl, int G, NnState* state,
+                              double* partial, double lr, double momentum, NnOpt* opt,
+                              double* scores) {
   hipError_t e = nn_allow_lds(dev::nn_grad_kernel);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(dev::nn_grad_kernel, dim3(G), dim3(kNnThreads),
                      sizeof(double) * (size_t)tl.doubles, st, X, y, n, net, tl, state, partial);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(dev::nn_update_g_kernel, dim3((net.P + kNnThreads - 1) / kNnThreads),
-                     dim3(kNnThreads), 0, st, partial, G, n, net.P, net.updater, lr, momentum,
-                     state, opt);
+  hipLaunchKernelGGL(opt ? dev::nn_update_kernel<true> : dev::nn_update_kernel<false>,
+                     nn_param_grid(net.P), dim3(kNnThreads), 0, st, partial, G, n, net.P,
+                     net.updater, lr, momentum, state, opt, scores);
   return hipGetLastError();
 }
 
@@ -987,8 +959,8 @@ hipError_t launch_nn_trial(hipStream_t st, const double* X, const double* y, int
                      partial);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(dev::nn_search_kernel, dim3((net.P + kNnThreads - 1) / kNnThreads),
-                     dim3(kNnThreads), 0, st, partial, G, n, net.P, max_ls, state, opt, search);
+  hipLaunchKernelGGL(dev::nn_search_kernel, nn_param_grid(net.P), dim3(kNnThreads), 0, st,
+                     partial, G, n, net.P, max_ls, state, opt, search);
   return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 0.5; runs bit-identical to each other, from host and from device rows; non-finite rows, refused
 labels, the statistics entry, and the train/test flow."""
 import math
-from ctypes import byref
+from ctypes import byref, c_int32
 
 import numpy as np
 import pytest
@@ -14,6 +14,7 @@ from eeg_dataanalysispackage_amd import _lib, pipeline
 from eeg_dataanalysispackage_amd import classification as clf
 from conftest import DOD02, INFO_TRAIN
 import nn_cases
+import nn_opt_cases
 import nn_reference as ref
 from test_nn_reference import ROUND_CASES, expected_counts
 
@@ -203,6 +204,57 @@ def test_refused_labels(ctx, mem):
             assert e.value.code == _lib.EEGFX_EINVAL and BAD_LABELS_TEXT in str(e.value)
             assert (pout == -7.25).all() and (sout == -7.25).all()
             ys[row] = keep
+
+
+def no_iterations_bad_label(mem):
+    """67 x 5 rows, widths (4, 2), label 40 = 0.5, a plain-SGD model asked for no iterations."""
+    name = "cg_tanh_lr10"
+    X, y, p0 = nn_opt_cases.data(name)
+    y = y.copy()
+    y[40] = 0.5
+    m = model_of(nn_opt_cases.CASES[name])
+    assert m.optimization_algo == "stochastic_gradient_descent" and X.shape == (67, 5)
+    return ((device(X), device(y)) if mem == DEV else (X, y)) + (p0, m)
+
+
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_no_iterations_still_validates_the_labels(ctx, mem):
+    """num_iterations = 0 under SGD: the rows are staged and the labels validated all the same."""
+    Xs, ys, p0, m = no_iterations_bad_label(mem)
+    pout = np.full(p0.size, -7.25)
+    with pytest.raises(fx.EegfxError) as e:
+        clf.nn_train(ctx, Xs, ys, m, p0, num_iterations=0, params_out=pout)
+    assert e.value.code == _lib.EEGFX_EINVAL and BAD_LABELS_TEXT in str(e.value)
+    assert (pout == -7.25).all()
+    ys[40] = 1.0
+    got, scores = clf.nn_train(ctx, Xs, ys, m, p0, num_iterations=0, params_out=pout)
+    assert got is pout and bits(pout) == bits(p0) and scores.shape == (0,)
+
+
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_no_iterations_still_validates_the_labels_through_nn_train_opt(ctx, mem):
+    """The same through eegfx_nn_train_opt under EEGFX_NN_OPT_SGD: neither search_out nor
+    *iterations_run is written."""
+    Xs, ys, p0, m = no_iterations_bad_label(mem)
+    pout = np.full(p0.size, -7.25)
+    search = np.full(3, -7.25).astype(clf.NN_SEARCH_DTYPE)
+    keep = search.copy()
+    with pytest.raises(fx.EegfxError) as e:
+        clf.nn_train_opt(ctx, Xs, ys, m, p0, num_iterations=0, params_out=pout,
+                         search_out=search[:0])
+    assert e.value.code == _lib.EEGFX_EINVAL and BAD_LABELS_TEXT in str(e.value)
+    cfg, o, run = m.struct(0), m.optimizer(), c_int32(-7)
+    assert o.algorithm == _lib.NN_OPTIMIZERS["stochastic_gradient_descent"]
+    call = lambda: ctx._call(mem, Xs, fx.lib().eegfx_nn_train_opt, ctx.handle, _lib.ptr(Xs),
+                             _lib.ptr(ys), 67, 5, byref(cfg), byref(o), _lib.ptr(p0), _lib.ptr(pout),
+                             None, _lib.ptr(search), byref(run), mem)
+    with pytest.raises(fx.EegfxError) as e:
+        call()
+    assert e.value.code == _lib.EEGFX_EINVAL and BAD_LABELS_TEXT in str(e.value)
+    assert (pout == -7.25).all() and bits(search) == bits(keep) and run.value == -7
+    ys[40] = 1.0
+    call()
+    assert bits(pout) == bits(p0) and bits(search) == bits(keep) and run.value == 0
 
 
 def test_argument_checks_before_any_device_call(ctx):

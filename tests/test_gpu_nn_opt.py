@@ -141,6 +141,25 @@ def test_no_iterations_returns_params0(ctx):
     assert bits(p) == bits(p0) and s.shape == (0,) and search.shape == (0,) and run == 0
 
 
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_no_iterations_does_no_device_work(ctx, mem):
+    """num_iterations = 0 under a line search returns params0 before anything is staged: a label
+    of 0.5 goes unseen (plain SGD refuses it), and params_out may be params0 itself."""
+    name = "cg_tanh_lr10"  # 67 x 5, widths (4, 2)
+    X, y, p0 = cases.data(name)
+    y = y.copy()
+    y[40] = 0.5
+    Xs, ys = (device(X), device(y)) if mem == DEV else (X, y)
+    m = model_of(cases.CASES[name])
+    assert m.optimization_algo == "conjugate_gradient" and X.shape == (67, 5)
+    p, s, search, run = nn_train_opt(ctx, Xs, ys, m, p0, num_iterations=0)
+    assert bits(p) == bits(p0) and s.shape == (0,) and search.shape == (0,) and run == 0
+    both = p0.copy()
+    p, s, search, run = nn_train_opt(ctx, Xs, ys, m, both, num_iterations=0, params_out=both)
+    assert p is both and bits(both) == bits(p0)
+    assert s.shape == (0,) and search.shape == (0,) and run == 0
+
+
 def test_entries_past_iterations_run_are_left(ctx):
     name = "lbfgs_zero_direction"  # 3 iterations asked, 1 run
     case = cases.CASES[name]

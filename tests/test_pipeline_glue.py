@@ -79,6 +79,41 @@ def test_classifier_base_guards_without_a_device():
         assert c._ctx is None  # no context was created on the way
 
 
+def test_classifier_statistics_of_host_rows_without_a_device():
+    """test / testFeatures on host rows, the prediction stubbed so that no device is used: the
+    network's statistics are reference_nn_statistics of its scores (a score that rounds to 2 is a
+    miss, the sums are kept), every other classifier's are reference_statistics."""
+    import numpy as np
+    from eeg_dataanalysispackage_amd import classification as clf
+
+    class Rows:  # a feature extraction that hands the epochs on as the feature rows
+        def extractFeaturesBatch(self, epochs):
+            return epochs
+
+    rows = np.arange(12.0).reshape(6, 2)
+    labels = [0.0, 0.0, 1.0, 1.0, 1.0, 0.0]
+    cases = ((clf.LogisticRegressionClassifier, [0.0, 1.0, 1.0, 0.0, 1.0, 0.0],
+              clf.reference_statistics),
+             (clf.NeuralNetworkClassifier, [0.25, 0.5, 0.75, 0.49, 1.5, -0.5],
+              clf.reference_nn_statistics))
+    for cls, out, reference in cases:
+        c = cls()
+        c._trained = lambda: True
+        c._predict_rows = lambda X, out=out: np.asarray(out)
+        c.setFeatureExtraction(Rows())
+        want = reference(out, labels)
+        for got in (c.testFeatures(rows, labels), c.test(rows, labels)):
+            assert type(got) is clf.ClassificationStatistics
+            assert (got.as_tuple(), got.MSE, got.class1sum, got.class2sum) == \
+                   (want.as_tuple(), want.MSE, want.class1sum, want.class2sum)
+        assert c._ctx is None
+    assert clf.reference_statistics(cases[0][1], labels).as_tuple() == (2, 2, 1, 1)
+    nn = clf.reference_nn_statistics(cases[1][1], labels)
+    # 0.5 rounds to 1 (a false positive), -0.5 to 0; 0.49 and 1.5 (-> 2) are false negatives
+    assert nn.as_tuple() == (1, 2, 1, 2)
+    assert nn.class1sum == 0.25 + 0.5 - 0.5 and nn.class2sum == 0.75 + 0.49 + 1.5
+
+
 def test_mllib_restatement_basics():
     import numpy as np
     from oracle import mllib_logreg as ref
