@@ -167,7 +167,7 @@ int extract_features_api(eegfx_ctx* ctx, const E* epochs, int64_t n, int32_t C, 
         // (features_small_kernel) reads them -- and writes the rows -- across the host link
         // directly: one launch and one stream sync, no DMA transfers (each costs a copy-engine
         // round trip) and no allocation once the context's staging has grown.  The rows are EXACT
-        // under both numerics (kernels.hip small_epoch), so the fma guard does not count them.
+        // under both numerics (small.hip small_epoch), so the fma guard does not count them.
         ctx->mb.stop_before_growth((size_t)n * C * row_w, out_bytes);
         double* hin = (double*)ctx->pin_in.get((size_t)n * C * row_w);
         double* hout = (double*)ctx->pin_out.get(out_bytes);

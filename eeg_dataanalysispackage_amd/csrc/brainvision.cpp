@@ -6,8 +6,8 @@
 //   readMarkerList(vmrk)        OffLineDataProvider.java:196
 // and restates the per-marker selection of OffLineDataProvider.java:200-265 (stimulus index,
 // out-of-range skip, target label, class balance) as eegfx_plan_markers.  The binary decode of
-// readBinaryData (:185-188) is fused into the device kernels (kernels.hip); this file only
-// moves the raw bytes.
+// readBinaryData (:185-188) is fused into the device kernels (cut.hip, fused.hip, wide.hip); this
+// file only moves the raw bytes.
 #include <sys/stat.h>
 
 #include <cctype>

@@ -1,15 +1,11 @@
-// kernels.hip -- gfx950 kernels of the epoch-to-feature path and their launchers.
-//
+// cut.hip -- the epoch writers of getData() (gfx950) and their launchers.
 //   cut_epochs_kernel            a3 + a5..a7: raw multiplexed samples -> baseline-corrected
 //                                epochs double[n][C][750]  (OffLineDataProvider.java:216-233)
-//   features_from_epochs_kernel  a11..a13: epochs -> L2-normalised dwt-8 features
-//                                (WaveletTransform.java:107-141, SignalProcessing.java:38-52)
-//   fused kernel                 see fused.hip (raw -> features, the benchmarked hot path)
-//   synth_kernel                 deterministic synthetic recordings for tests and bench.py
+//   cut_write_*_kernel           the same write pass after the staged baseline kernels, by layout
+//   cut_features_c3_kernel       the epochs and their dwt-8 rows in one pass (3-channel file)
 //   narrow_epochs_kernel         resident double epochs -> float32 (eegfx_odp_get_data_f32)
-// The epoch writers and readers take the epochs' element type as a template parameter E: double
-// (the reference's double[n][C][750]) or float (the fp32 values it widens, the *_f32 entries).
-//
+// The epoch writers take the epochs' element type as a template parameter E: double (the
+// reference's double[n][C][750]) or float (the fp32 values it widens, the *_f32 entries).
 // Compiled with -ffp-contract=off: every fp32/fp64 expression is evaluated as written, one
 // correctly rounded IEEE operation at a time, matching the Java (strictfp-equivalent) order.
 #include <hip/hip_runtime.h>
@@ -72,6 +68,79 @@ __device__ __forceinline__ void store_f32_rows(float* __restrict__ o, int C, int
   }
 }
 
+// The same rows as doubles: lane t stores pair q of channel row c, frames 2q and 2q + 1, as one
+// 16-byte store (nf is even, so a pair never straddles two rows); (c, q) steps by 256 pairs.
+template <typename V>
+__device__ __forceinline__ void store_f64_rows(double* __restrict__ o, int C, int nf, int t, V value) {
+  const int hp = nf / 2, npairs = C * hp, sc = 256 / hp, sq = 256 % hp;
+  int c = t / hp, q = t - (t / hp) * hp;
+  for (int idx = t; idx < npairs; idx += 256) {
+    const int f = 2 * q;
+    *(double2*)(o + (int64_t)c * kPost + f) = make_double2((double)value(c, f), (double)value(c, f + 1));
+    c += sc;
+    q += sq;
+    if (q >= hp) { q -= hp; ++c; }
+  }
+}
+template <typename E, typename V>
+__device__ __forceinline__ void store_rows(E* __restrict__ o, int C, int nf, int t, V value) {
+  if constexpr (std::is_same<E, float>::value) store_f32_rows(o, C, nf, t, value);
+  else store_f64_rows(o, C, nf, t, value);
+}
+
+// OffLineDataProvider.java:220-225 (see fused.hip position_ok): an invalid position is cut as
+// pos = 100.  The baseline kernels flag it (cut_epochs_kernel, which has none before it, itself).
+__device__ __forceinline__ int64_t cut_position(int64_t p0, int64_t n_frames) {
+  return p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;
+}
+
+// The one decode: a sample inside the recording is the reference's (float)raw * res, and
+// Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f; smp() is not evaluated there).
+// The second form reads frame f, column col of the multiplexed recording.
+template <typename Smp>
+__device__ __forceinline__ float decode(bool inside, float res, Smp smp) {
+  return inside ? (float)smp() * res : 0.0f;
+}
+template <typename T, typename I>
+__device__ __forceinline__ float decode(const T* raw, I f, int64_t n_frames, int ct, int col,
+                                        float res) {
+  return decode(f >= 0 && f < n_frames, res, [&] { return raw[f * ct + col]; });
+}
+
+// Lanes 0..C-1 put the channel parameters and the epoch's C baselines into LDS (no barrier here).
+__device__ __forceinline__ void stage_channels(const ChanSel& sel, const float* __restrict__ base, int C,
+                                               int t, int* s_col, float* s_res, float* s_base) {
+  if (t < C) {
+    s_col[t] = sel.col[t];
+    s_res[t] = sel.res[t];
+    s_base[t] = base[t];
+  }
+}
+
+// The bytes of packed int16 frames as they lie: dwords [a0, a0 + total) of the recording to
+// `stage`, 8 loads in flight per thread.  The dword holding the recording's last two bytes
+// (nbytes in all) is read as a half, so no load passes its end; dwords past it stage as 0.
+__device__ __forceinline__ void stage_packed(uint32_t* stage, const int16_t* __restrict__ raw,
+                                             int64_t a0, int total, int64_t nbytes, int t) {
+  const uint32_t* src = (const uint32_t*)raw;
+  for (int k0 = 0; k0 < total; k0 += 8 * 256) {
+    uint32_t v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = k0 + 256 * u + t;
+      const int64_t a = (a0 + k) * 4;
+      v[u] = 0u;
+      if (k < total) {
+        if (a + 4 <= nbytes) v[u] = src[a0 + k];
+        else if (a + 2 <= nbytes) v[u] = (uint16_t)raw[(a >> 1)];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (k0 + 256 * u + t < total) stage[k0 + 256 * u + t] = v[u];
+  }
+}
+
 // a3 + a5..a7.  One workgroup per epoch.  Lanes 0..C-1 fold the 100 pre-stimulus samples of
 // their channel sequentially in fp32 (Baseline.java:29-42 -- order-exact, so no tree reduction),
 // then all lanes write the 750 post-stimulus samples, coalesced.
@@ -84,39 +153,30 @@ __global__ __launch_bounds__(256) void cut_epochs_kernel(const T* __restrict__ r
   __shared__ float base[kMaxChannels];
   const int64_t e = blockIdx.x;
   const int64_t p0 = pos[e];
-  // OffLineDataProvider.java:220-225 (see fused.hip position_ok): an invalid position is flagged
-  // and cut as pos = 100
-  const bool ok = p0 >= kPre && p0 - kPre <= n_frames;
+  const bool ok = p0 >= kPre && p0 - kPre <= n_frames;  // an invalid position is flagged here
   if (threadIdx.x == 0 && !ok && err)
     __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const int64_t p = ok ? p0 : kPre;
+  const int64_t p = cut_position(p0, n_frames);
   const int64_t lo = p - kPre;
   if ((int)threadIdx.x < C) {
     const int c = threadIdx.x;
     const int col = sel.col[c];
     const float r = sel.res[c];
     float b = 0.0f;
-    for (int i = 0; i < kPre; ++i) {
-      const int64_t f = lo + i;
-      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f).
-      const float v = (f >= 0 && f < n_frames) ? (float)raw[f * ct + col] * r : 0.0f;
-      b = b + v;
-    }
+    for (int i = 0; i < kPre; ++i) b = b + decode(raw, lo + i, n_frames, ct, col, r);
     base[c] = b / (float)kPre;
   }
   __syncthreads();
   E* o = out + e * C * kPost;
   for (int idx = threadIdx.x; idx < C * kPost; idx += blockDim.x) {
     const int c = idx / kPost;
-    const int64_t f = p + (idx - c * kPost);
-    const float v = (f >= 0 && f < n_frames) ? (float)raw[f * ct + sel.col[c]] * sel.res[c] : 0.0f;
+    const float v = decode(raw, p + (idx - c * kPost), n_frames, ct, sel.col[c], sel.res[c]);
     o[idx] = (E)(v - base[c]);  // this fallback stores single samples for both element types
   }
 }
 
 // a5..a7 write pass of the materialised epochs (getData()): the per-(epoch, channel) baselines
-// come from the LDS-staged baseline kernels; each lane writes two consecutive samples of one
-// channel row as one 16-byte store (750 is even, so a pair never straddles two rows).
+// come from the LDS-staged baseline kernels; the samples are read straight from the recording.
 template <typename T, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_kernel(const T* __restrict__ raw, int64_t n_frames,
                                                         int ct, ChanSel sel, int C,
@@ -124,28 +184,10 @@ __global__ __launch_bounds__(256) void cut_write_kernel(const T* __restrict__ ra
                                                         const float* __restrict__ base,
                                                         E* __restrict__ out) {
   const int64_t e = blockIdx.x;
-  const int64_t p0 = pos[e];
-  const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
-  E* o = out + e * C * kPost;
-  if constexpr (std::is_same<E, float>::value) {
-    store_f32_run<256>(o, C * kPost, (int)threadIdx.x, [&](int c, int fi) {
-      const int64_t f = p + fi;
-      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-      const float v = f >= 0 && f < n_frames ? (float)raw[f * ct + sel.col[c]] * sel.res[c] : 0.0f;
-      return v - base[e * C + c];
-    });
-  } else {
-    for (int idx = 2 * (int)threadIdx.x; idx < C * kPost; idx += 2 * (int)blockDim.x) {
-      const int c = idx / kPost;
-      const int64_t f = p + (idx - c * kPost);
-      const int col = sel.col[c];
-      const float r = sel.res[c], b = base[e * C + c];
-      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-      const float v0 = f >= 0 && f < n_frames ? (float)raw[f * ct + col] * r : 0.0f;
-      const float v1 = f + 1 >= 0 && f + 1 < n_frames ? (float)raw[(f + 1) * ct + col] * r : 0.0f;
-      *(double2*)(o + idx) = make_double2((double)(v0 - b), (double)(v1 - b));
-    }
-  }
+  const int64_t p = cut_position(pos[e], n_frames);
+  store_rows(out + e * C * kPost, C, kPost, (int)threadIdx.x, [&](int c, int f) {
+    return decode(raw, p + f, n_frames, ct, sel.col[c], sel.res[c]) - base[e * C + c];
+  });
 }
 
 // The same write pass for epochs of at most kCutPairs * 256 sample pairs (C <= 3): the channel
@@ -163,20 +205,13 @@ __global__ __launch_bounds__(256) void cut_write_small_kernel(
   __shared__ float s_res[kMaxChannels], s_base[kMaxChannels];
   const int t = threadIdx.x;
   const int64_t e = blockIdx.x;
-  if (t < C) {
-    s_col[t] = sel.col[t];
-    s_res[t] = sel.res[t];
-    s_base[t] = base[e * C + t];
-  }
-  const int64_t p0 = pos[e];
-  const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
+  stage_channels(sel, base + e * C, C, t, s_col, s_res, s_base);
+  const int64_t p = cut_position(pos[e], n_frames);
   __syncthreads();
   E* o = out + e * C * kPost;
   if constexpr (std::is_same<E, float>::value) {  // at most 640 quads: three trips
-    store_f32_run<256>(o, C * kPost, t, [&](int c, int fi) {
-      const int64_t f = p + fi;
-      const float v = f >= 0 && f < n_frames ? (float)raw[f * ct + s_col[c]] * s_res[c] : 0.0f;
-      return v - s_base[c];
+    store_f32_run<256>(o, C * kPost, t, [&](int c, int f) {
+      return decode(raw, p + f, n_frames, ct, s_col[c], s_res[c]) - s_base[c];
     });
   } else {
     const int npairs = C * (kPost / 2);  // <= 256 * kCutPairs (launcher)
@@ -190,9 +225,8 @@ __global__ __launch_bounds__(256) void cut_write_small_kernel(
         const int64_t f = p + 2 * (idx - c * (kPost / 2));
         const int col = s_col[c];
         const float r = s_res[c];
-        // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-        if (f >= 0 && f < n_frames) v0[u] = (float)raw[f * ct + col] * r;
-        if (f + 1 >= 0 && f + 1 < n_frames) v1[u] = (float)raw[(f + 1) * ct + col] * r;
+        v0[u] = decode(raw, f, n_frames, ct, col, r);
+        v1[u] = decode(raw, f + 1, n_frames, ct, col, r);
       }
     }
 #pragma unroll
@@ -369,8 +403,7 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
   const int ne = n - e0 < kCfEpochs ? (int)(n - e0) : kCfEpochs;
   const int64_t nbytes = n_frames * FB;
   if (tid < kCfEpochs) {
-    const int64_t p0 = tid < ne ? pos[e0 + tid] : kPre;
-    const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
+    const int64_t p = cut_position(tid < ne ? pos[e0 + tid] : kPre, n_frames);
     sA[tid] = (p * FB) >> 2;
     sH[tid] = (int)((p * FB) & 3) >> 1;
     sP[tid] = p;
@@ -381,8 +414,7 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
   }
   if (tid < kCfEpochs * C) s_base[tid] = tid < ne * C ? base[e0 * C + tid] : 0.0f;
   __syncthreads();
-  {  // 1. stage (8 loads in flight per thread; the dword holding the recording's last two bytes
-     //    is read as a half, nothing past the end)
+  {  // 1. stage: stage_packed's loop with this kernel's (epoch m, dword d) -> skewed LDS mapping
     const uint32_t* src = (const uint32_t*)raw;
     constexpr int TOTAL = kCfEpochs * kCfDwords;
     for (int k0 = 0; k0 < TOTAL; k0 += 8 * 256) {
@@ -513,6 +545,8 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
 #define EEGFX_CUT_LDS_MAX (64 * 1024)
 #endif
 constexpr int kCutLdsMax = EEGFX_CUT_LDS_MAX;
+// The rows keep this kernel's own loops: written through store_rows and decode, its staging loop
+// compiled to nested branches and the 32-channel cut took 2.326 ms against 2.301.
 template <typename T, bool FEAT = false, bool FAST = false, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_lds_kernel(
     const T* __restrict__ raw, int64_t n_frames, int ct, ChanSel sel, int C,
@@ -530,8 +564,7 @@ __global__ __launch_bounds__(256) void cut_write_lds_kernel(
     s_res[t] = sel.res[t];
     s_base[t] = base[e * C + t];
   }
-  const int64_t p0 = pos[e];
-  const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
+  const int64_t p = cut_position(pos[e], n_frames);
   const int FW = ct * (int)sizeof(T) / 4, FS = FW + 1;
   const int64_t g0 = p + f0;  // first frame of this chunk
   const uint32_t* src = (const uint32_t*)raw;
@@ -614,7 +647,6 @@ __global__ __launch_bounds__(256) void cut_write_lds_kernel(
 // 3-channel path of configs[0]-[2]: 6-byte frames): the chunk's bytes are staged as they lie, from
 // the dword that holds its first frame, without per-frame padding; lanes reading the sample pairs
 // of one channel are 2 frames apart (3 dwords at 3 channels: an odd stride, no bank conflicts).
-// The dword holding the recording's last two bytes is read as a half so no load passes its end.
 template <bool FEAT = false, bool FAST = false, typename E = double>
 __global__ __launch_bounds__(256) void cut_write_lds_packed_kernel(
     const int16_t* __restrict__ raw, int64_t n_frames, int ct, ChanSel sel, int C,
@@ -627,459 +659,25 @@ __global__ __launch_bounds__(256) void cut_write_lds_packed_kernel(
   const int64_t e = blockIdx.x;
   const int f0 = (int)blockIdx.y * nfc;
   const int nf = kPost - f0 < nfc ? kPost - f0 : nfc;
-  if (t < C) {
-    s_col[t] = sel.col[t];
-    s_res[t] = sel.res[t];
-    s_base[t] = base[e * C + t];
-  }
-  const int64_t p0 = pos[e];
-  const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : kPre;  // flagged by the baselines
+  stage_channels(sel, base + e * C, C, t, s_col, s_res, s_base);
+  const int64_t p = cut_position(pos[e], n_frames);
   const int64_t g0 = p + f0;
   const int FB = 2 * ct;
-  const int64_t nbytes = n_frames * FB;
   const int64_t b0 = g0 * FB;                 // first byte of the chunk
-  const int64_t a0 = b0 >> 2;                 // its dword
   const int delta = (int)(b0 & 3);            // 0 or 2
   const int total = (delta + nf * FB + 3) >> 2;
-  const uint32_t* src = (const uint32_t*)raw;
-  for (int k0 = 0; k0 < total; k0 += 8 * 256) {
-    uint32_t v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = k0 + 256 * u + t;
-      const int64_t a = (a0 + k) * 4;
-      v[u] = 0u;
-      if (k < total) {
-        if (a + 4 <= nbytes) v[u] = src[a0 + k];
-        else if (a + 2 <= nbytes) v[u] = (uint16_t)raw[(a >> 1)];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (k0 + 256 * u + t < total) stage[k0 + 256 * u + t] = v[u];
-  }
+  stage_packed(stage, raw, b0 >> 2, total, n_frames * FB, t);
   __syncthreads();
   const int16_t* h = (const int16_t*)((const uint8_t*)stage + delta);
-  if constexpr (std::is_same<E, float>::value) {
-    store_f32_rows(out + e * C * kPost + f0, C, nf, t, [&](int c, int f) {
-      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-      const float v = g0 + f < n_frames ? (float)h[f * ct + s_col[c]] * s_res[c] : 0.0f;
-      return v - s_base[c];
-    });
-  } else {
-    const int hp = nf / 2, npairs = C * hp, sc = 256 / hp, sq = 256 % hp;
-    int c = t / hp, q = t - (t / hp) * hp;
-    double* o = out + e * C * kPost + f0;
-    for (int idx = t; idx < npairs; idx += 256) {
-      const int col = s_col[c];
-      const float r = s_res[c], b = s_base[c];
-      const int f = 2 * q;
-      // Arrays.copyOfRange zero-pads past the end (toFloatArray -> 0.0f)
-      const float v0 = g0 + f < n_frames ? (float)h[f * ct + col] * r : 0.0f;
-      const float v1 = g0 + f + 1 < n_frames ? (float)h[(f + 1) * ct + col] * r : 0.0f;
-      *(double2*)(o + (int64_t)c * kPost + f) = make_double2((double)(v0 - b), (double)(v1 - b));
-      c += sc;
-      q += sq;
-      if (q >= hp) { q -= hp; ++c; }
-    }
-  }
+  store_rows(out + e * C * kPost + f0, C, nf, t, [&](int c, int f) {
+    return decode(g0 + f < n_frames, s_res[c], [&] { return h[f * ct + s_col[c]]; }) - s_base[c];
+  });
   if constexpr (FEAT) {  // one chunk per epoch (launcher): the window frames are staged
     double* gx = (double*)((uint8_t*)stage + staged_features_lds((size_t)total * 4, C) - 64 * 8 - 16);
     staged_features<FAST, false>(
         [&](int f, int col) { return (float)h[f * ct + col]; },
-        [&](int f, int col) {
-          return g0 + f < n_frames ? (float)raw[(g0 + f) * ct + col] : 0.0f;
-        },
+        [&](int f, int col) { return g0 + f < n_frames ? (float)raw[(g0 + f) * ct + col] : 0.0f; },
         s_col, s_res, s_base, C, (double*)stage, gx, gx + 64, fout + e * 16 * C, guard, t);
-  }
-}
-
-// a11..a13 from materialised epochs.  One wave per workgroup owns 8 epochs and walks their
-// channels; lane = 8*epoch + segment (dwt8.h).  For each channel the wave reads the 8 windows
-// (512 doubles each, contiguous in the epoch rows) with 16-byte loads, 1 KB of one window per
-// load instruction, and writes them to LDS in a bank-skewed layout: segment s of window g at
-// g*kFeWin + s*kFeSeg doubles.  kFeSeg = 65 doubles (130 dwords, 2 mod 64) and kFeWin = 520
-// (1,040 dwords, 16 mod 64), so the ds_read_b64 of lane (g, s) for any sample index falls on
-// banks 16g + 2s (+1) plus a common offset: the 32 lanes of a half-wave use 64 distinct banks.
-// (Each lane reading its own 512 contiguous bytes straight from memory touches 64 cache lines
-// per load instruction; that pattern moved ~1.9 TB/s.)  The filter bank then runs from LDS: FMA
-// the collapsed four-point filter of dwt8_collapsed_core on the doubles as they are, EXACT the
-// level-by-level cascade with value halos.  Features collect in LDS, are normalised per epoch
-// with the reference's sequential sum of squares and written coalesced.  33 KB of windows per
-// workgroup: 4 workgroups per CU.
-constexpr int kFeSeg = kSegLen + 1;
-constexpr int kFeWin = 8 * kFeSeg;
-constexpr size_t kFeWinBytes = sizeof(double) * 8 * kFeWin;
-typedef double f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-
-// Under fma numerics each lane also keeps the largest |x| of its samples, and the rows are
-// checked against the conditioning guard (guard.h: sum over the channels of the measured X^2); a
-// row that fails is recomputed under EXACT by the wave from the epochs in memory, the window LDS
-// as scratch (rare).
-// ROWS_OUT (wide rows, launcher): the 8 feature rows (8 F doubles: 32 KB at C = 32) do not stay in
-// LDS, where they halved the resident workgroups.  After each channel the 8 x nfeat values pass
-// through a 1 KB LDS tile, leave as whole 128-byte runs into `out`, and lanes 0-7 add their
-// squares to the epoch's sum in index order (the reference's sequential sum,
-// SignalProcessing.java:38-52); at the end the wave rescales its rows in place (L2-resident).
-//
-// Float32 epochs (E = float, eegfx_extract_features_f32 and the scratch epochs of
-// eegfx_process_recording_fe): a window is 2 KB, read as 16 loads of four floats per lane (quad
-// q = 64 (j % 2) + lane of window j / 2), again 1 KB of one window per load instruction.  The
-// window starts at ep + 4 (row * row_stride + skip) bytes, on any 4-byte boundary, so the quads
-// are typed 4-byte aligned, as the double pairs are typed 8-byte aligned (an odd skip): the
-// 16-byte global load takes any dword address.  The samples are widened as they are written into
-// the same LDS layout, and everything after that is the double kernel's: the rows are its rows.
-typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-template <bool FAST, bool ROWS_OUT, typename E = double>
-__global__ __launch_bounds__(64) void features_from_epochs_kernel(const E* __restrict__ ep,
-                                                                  int64_t n, int C, int skip,
-                                                                  int nfeat, int row_stride,
-                                                                  double* __restrict__ out,
-                                                                  Guard guard) {
-  constexpr bool F32 = std::is_same<E, float>::value;
-  __shared__ __attribute__((aligned(16))) double win[8 * kFeWin];
-  extern __shared__ __attribute__((aligned(16))) double fsmem[];
-  const int lane = threadIdx.x;
-  const int el = lane >> 3, s = lane & 7;
-  const int F = C * nfeat;
-  double* feat = fsmem;                             // [8][F], or the [8][16] tile (ROWS_OUT)
-  double* norm = feat + (ROWS_OUT ? 8 * 16 : 8 * F);  // [8]
-  const int64_t e0 = (int64_t)blockIdx.x * 8;
-  const int64_t ne = (n - e0) < 8 ? (n - e0) : 8;
-  double* o = out + e0 * F;
-  // quad q = 64 (j % 4) + lane of window j / 4: doubles 2q, 2q + 1 of segment q / 32.  Epochs
-  // past n read the last epoch's window (the loads stay unconditional; the result is dropped).
-  // Channel c + 1's windows are in flight while channel c runs the filter bank.
-  constexpr int NV = F32 ? 16 : 32;
-  typename std::conditional<F32, f32x4_a4, f64x2_a8>::type v[NV];
-  auto load = [&](int c) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      if constexpr (F32) {
-        const int g = j >> 1;
-        const int64_t e = e0 + (g < ne ? g : ne - 1);
-        const int q = ((j & 1) << 6) | lane;
-        v[j] = __builtin_nontemporal_load(
-            (const f32x4_a4*)(ep + (e * C + c) * row_stride + skip + 4 * q));
-      } else {
-        const int g = j >> 2;
-        const int64_t e = e0 + (g < ne ? g : ne - 1);
-        const int q = ((j & 3) << 6) | lane;
-        v[j] = __builtin_nontemporal_load(
-            (const f64x2_a8*)(ep + (e * C + c) * row_stride + skip + 2 * q));
-      }
-    }
-  };
-  load(0);
-  double sx = 0.0;   // fma: sum over the channels of this lane's signal's X^2
-  double acc = 0.0;  // ROWS_OUT, lanes < ne: epoch `lane`'s sum of squares so far
-  for (int c = 0; c < C; ++c) {
-    wave_sync();  // the previous channel's LDS reads precede these writes
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      if constexpr (F32) {  // floats 4q .. 4q + 3 of segment q / 16, widened
-        const int q = ((j & 1) << 6) | lane;
-        double* d = win + (j >> 1) * kFeWin + (q >> 4) * kFeSeg + 4 * (q & 15);
-        d[0] = (double)v[j].x;
-        d[1] = (double)v[j].y;
-        d[2] = (double)v[j].z;
-        d[3] = (double)v[j].w;
-      } else {
-        const int q = ((j & 3) << 6) | lane;
-        double* d = win + (j >> 2) * kFeWin + (q >> 5) * kFeSeg + 2 * (q & 31);
-        d[0] = v[j].x;
-        d[1] = v[j].y;
-      }
-    }
-    wave_sync();
-    if (c + 1 < C) load(c + 1);
-    const double* own = win + el * kFeWin + s * kFeSeg;
-    double a6, d6;
-    if constexpr (FAST) {
-      double xm = 0.0;
-      dwt8_collapsed_core([&](int k) { return own[k]; },
-                          [&](double v0, double v1, double& x0, double& x1) {
-                            xm = fmax(xm, fmax(fabs(v0), fabs(v1)));
-                            x0 = v0;
-                            x1 = v1;
-                          },
-                          lane & ~7, s, a6, d6);
-      xm = group8_max(xm);
-      const double x2 = xm * xm;  // doubles below 2^-537 square to 0: keep X^2 != 0 (guard.h)
-      sx += x2 == 0.0 && xm != 0.0 ? 0x1p-1022 : x2;
-    } else {
-      const double* sig = win + el * kFeWin;
-      double x[kIn];
-#pragma unroll
-      for (int k = 0; k < kIn; ++k) x[k] = k < kSegLen ? own[k] : sig[((s + 1) & 7) * kFeSeg + k - kSegLen];
-      dwt8_cascade<false, true>(x, nullptr, lane & ~7, s, a6, d6);
-    }
-    if constexpr (ROWS_OUT) {
-      feat[el * 16 + s] = a6;  // the tile's previous reads finished before the window writes
-      feat[el * 16 + 8 + s] = d6;
-      wave_sync();
-      for (int idx = lane; idx < ne * nfeat; idx += 64) {
-        const int e = idx / nfeat, j = idx - e * nfeat;
-        o[(int64_t)e * F + c * nfeat + j] = feat[e * 16 + j];
-      }
-      if (lane < ne)
-        for (int j = 0; j < nfeat; ++j) {
-          const double f = feat[lane * 16 + j];
-          acc = acc + f * f;  // Math.pow(f, 2) summed in index order
-        }
-    } else if (el < ne) {
-      if (s < nfeat) feat[el * F + c * nfeat + s] = a6;
-      if (8 + s < nfeat) feat[el * F + c * nfeat + 8 + s] = d6;
-    }
-  }
-  wave_sync();
-  const double sx_row = __shfl(sx, (lane & 7) * 8, 64);  // epoch `lane`'s X^2 sum (lanes < 8)
-  bool fails = false;
-  if (lane < ne) {
-    if constexpr (!ROWS_OUT) {
-      for (int i = 0; i < F; ++i) {
-        const double f = feat[lane * F + i];
-        acc = acc + f * f;  // Math.pow(f, 2) summed in index order
-      }
-    }
-    norm[lane] = sqrt(acc);
-    // caller-supplied doubles: also the rows whose norm the squares cannot carry (guard.h)
-    fails = FAST && guard.total && (guard_fails(acc, kGuardK2Collapsed, sx_row) ||
-                                    guard_acc_out_of_range(acc, sx_row));
-  }
-  if constexpr (FAST) {  // the guard's rare path: flagged rows recomputed under EXACT in place
-    uint64_t flagged = __ballot(fails);
-    if (flagged) {
-      wave_sync();
-      if (lane == 0) {  // the only test is the measured one: its failures count as both
-        guard_count_rechecked(guard, __popcll(flagged));
-        guard_count_recomputed(guard, (unsigned long long)__popcll(flagged));
-      }
-      do {
-        const int e = __ffsll((unsigned long long)flagged) - 1;
-        const E* row = ep + (e0 + e) * C * (int64_t)row_stride + skip;
-        static_assert(768 + kMaxChannels * 16 <= 8 * kFeWin, "the recomputed row fits the windows");
-        double* dst = ROWS_OUT ? win + 768 : feat + e * F;  // past the 768-double scratch
-        dwt8_exact_row_wave(
-            [&](int c, int k) { return (double)row[(int64_t)c * row_stride + k]; }, C, nfeat, win,
-            dst, lane);
-        if constexpr (ROWS_OUT) {
-          wave_sync();
-          for (int i = lane; i < F; i += 64) o[(int64_t)e * F + i] = dst[i];
-          wave_sync();
-        }
-        if (lane == 0) norm[e] = 1.0;  // the row is normalised
-        flagged &= flagged - 1;
-      } while (flagged);
-    }
-  }
-  wave_sync();
-  if constexpr (ROWS_OUT) {
-    __threadfence_block();  // this wave's raw rows are complete before it reads them back
-    for (int e = 0; e < ne; ++e) {  // eight loads in flight per batch (L2 round trips)
-      double* r = o + (int64_t)e * F;
-      const double nv = norm[e];
-      for (int i0 = 0; i0 < F; i0 += 8 * 64) {
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int i = i0 + 64 * u + lane;
-          t[u] = i < F ? r[i] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int i = i0 + 64 * u + lane;
-          if (i < F) r[i] = t[u] / nv;
-        }
-      }
-    }
-  } else {
-    for (int idx = lane; idx < ne * F; idx += 64) o[idx] = feat[idx] / norm[idx / F];
-  }
-}
-
-// a11..a13 for small host batches (the per-epoch IFeatureExtraction drop-in): one workgroup per
-// epoch reads the epoch's packed window rows (C x 512 doubles, pinned host memory mapped into the
-// device) with 16-byte loads, all issued before the first wait -- one host-link round trip instead
-// of the 72 dependent-free but scattered 8-byte loads per lane of features_from_epochs_kernel --
-// stages them in LDS, runs each channel's six levels on a whole wave (dwt8_exact_signal_wave,
-// channels dealt over the four waves), normalises, and writes the row back across the link.
-// C <= kSmallMaxC.
-//
-// One epoch on one workgroup is a latency problem, not a throughput one, so this path computes
-// EXACT numerics under both settings: the whole-wave levels keep each lane's dependent chain short
-// (~190 operations) where the batch kernels' 8-lanes-per-signal fma cascade runs ~1,200 per lane,
-// and an EXACT row needs no conditioning guard.  Under fma numerics the rows are therefore the
-// EXACT ones (inside the 1e-9 contract by definition); the guard's counters do not count them.
-constexpr int kSmallMaxC = 16;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "features_small_kernel stages 80 KB of LDS per workgroup: gfx950 (160 KB per CU) only"
-#endif
-struct SmallLds {
-  double xs[kSmallMaxC * kWin];
-  double scr[4][384];  // per-wave level scratch (dwt8_exact_signal_wave)
-  double feat[kSmallMaxC * 16];
-  double norm;
-};
-static_assert(sizeof(SmallLds) <= 160 * 1024, "features_small_kernel's LDS exceeds one gfx950 CU");
-
-// One epoch (its C x 512 window doubles at `src`, 16-byte aligned) -> its row at `dst`, by a
-// workgroup of 256 threads (uniform control flow; ends with a barrier).
-__device__ __forceinline__ void small_epoch(const double* __restrict__ src_rows, int C, int nfeat,
-                                            double* __restrict__ dst, SmallLds& sh) {
-  typedef double f64x2 __attribute__((ext_vector_type(2)));
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const f64x2* src = (const f64x2*)src_rows;
-  const int npairs = C * kWin / 2;  // <= 4096: at most 16 per thread
-  f64x2 v[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int i = tid + 256 * k;
-    if (i < npairs) v[k] = src[i];
-  }
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int i = tid + 256 * k;
-    if (i < npairs) *(f64x2*)(sh.xs + 2 * i) = v[k];
-  }
-  __syncthreads();
-  const int F = C * nfeat;
-  for (int c = w; c < C; c += 4) {  // uniform per wave
-    const double f = dwt8_exact_signal_wave(sh.xs + c * kWin, sh.scr[w], lane);
-    if (lane < nfeat) sh.feat[c * nfeat + lane] = f;
-  }
-  __syncthreads();
-  // SignalProcessing.normalize: Math.pow(f, 2) summed in index order.  Wave 0 squares 64
-  // features at a time, one per lane, and the running sum walks the lanes in order (readlane),
-  // so the additions are the reference's, in its order, without a serial LDS round trip each.
-  if (w == 0) {
-    double acc = 0.0;
-    for (int base = 0; base < F; base += 64) {
-      const int i = base + lane;
-      const double sq = i < F ? sh.feat[i] * sh.feat[i] : 0.0;
-      const int m = F - base < 64 ? F - base : 64;
-      for (int j = 0; j < m; ++j) acc = acc + lane_value(sq, j);
-    }
-    if (lane == 0) sh.norm = sqrt(acc);
-  }
-  __syncthreads();
-  for (int i = tid; i < F; i += 256) dst[i] = sh.feat[i] / sh.norm;
-  __syncthreads();  // sh is reused by the next epoch
-}
-
-__global__ __launch_bounds__(256) void features_small_kernel(const double* __restrict__ rows,
-                                                             int C, int nfeat,
-                                                             double* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) SmallLds sh;
-  const int64_t e = blockIdx.x;
-  small_epoch(rows + e * C * kWin, C, nfeat, out + e * C * nfeat, sh);
-}
-
-// The opt-in resident form of the same path (eegfx_ctx_set_mailbox): one workgroup that stays on
-// the device and serves the context's small host batches without a launch each.  Wave 0 polls
-// the 64-bit request word of a host-mapped MailboxCmd (system-scope atomic loads, a short s_sleep
-// between polls; the word carries the sequence number and the whole request); a new request's
-// epochs are read from its pinned rows, computed by small_epoch exactly as
-// features_small_kernel does, and written to its pinned output, then the completed sequence
-// number is published (system-scope release after every wave's stores).  The kernel returns when
-// the host sets `stop`, or after idle_ticks (s_memrealtime, 100 MHz) without a request -- every
-// wave reaches that exit; the host relaunches it on the next request.  At entry it publishes its
-// launch generation in `alive`: the host posts a request only to a server that has started (a
-// kernel still queued behind other work is never handed a request the launch path might also
-// serve).
-__global__ __launch_bounds__(256) void features_mailbox_kernel(MailboxCmd* mb, uint64_t idle_ticks,
-                                                               uint32_t gen) {
-  __shared__ __attribute__((aligned(16))) SmallLds sh;
-  __shared__ uint32_t cmd[2];  // request to serve, 0 = return
-  const int tid = threadIdx.x;
-  // Control flow stays wave-uniform throughout: wave 0 polls with all 64 lanes (one request per
-  // poll, the loaded word made uniform with readfirstlane).  A lane-divergent `if (tid == 0)`
-  // poll at the loop top let the compiler structurise the loop so that lanes other than 0 went
-  // round the served request again instead of waiting at the barrier -- the server then never
-  // answered.
-  const bool wave0 = __builtin_amdgcn_readfirstlane(tid >> 6) == 0;
-  uint32_t last = (uint32_t)__builtin_amdgcn_readfirstlane(
-      (int)__hip_atomic_load(&mb->done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
-  const double* rows = mb->rows;
-  double* out = mb->out;
-  if (tid == 0) __hip_atomic_store(&mb->alive, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  for (;;) {
-    if (wave0) {
-      uint64_t go = 0;
-      const uint64_t t0 = wall_clock64();
-      for (;;) {
-        // both words in one round trip across the link: relaxed loads issued back to back (an
-        // acquire load would wait for its value before the second load); the acquire is the
-        // system-scope fence every wave runs once a request is seen
-        const uint64_t r = __hip_atomic_load(&mb->req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const uint32_t st = __hip_atomic_load(&mb->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(r >> 32));
-        if (hi != last) {
-          go = (uint64_t)hi << 32 | lo;
-          break;
-        }
-        if (__builtin_amdgcn_readfirstlane((int)st)) break;
-        if (wall_clock64() - t0 > idle_ticks) break;
-        __builtin_amdgcn_s_sleep(2);
-      }
-      if (tid == 0) {
-        cmd[0] = (uint32_t)(go >> 32);
-        cmd[1] = (uint32_t)go;
-      }
-    }
-    __syncthreads();
-    const uint32_t seq = (uint32_t)__builtin_amdgcn_readfirstlane((int)cmd[0]);
-    if (seq == 0) break;  // stop or idle
-    const uint32_t word = (uint32_t)__builtin_amdgcn_readfirstlane((int)cmd[1]);
-    const int C = (int)((word >> 26) & 31) + 1, nfeat = (int)((word >> 21) & 31) + 1;
-    const int64_t n = (int64_t)(word & ((1u << 21) - 1));
-    // every wave: no stale line of the (reused) pinned rows from an earlier request
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    for (int64_t e = 0; e < n; ++e)
-      small_epoch(rows + e * C * kWin, C, nfeat, out + e * C * nfeat, sh);
-    __threadfence_system();  // this thread's rows reach the host before the flag below
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&mb->done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    last = seq;
-  }
-}
-
-// ---- synthetic recordings ------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ float unit_noise(uint64_t seed, uint64_t key) {  // [-1, 1)
-  return (float)(splitmix64(seed ^ splitmix64(key)) >> 40) * (2.0f / 16777216.0f) - 1.0f;
-}
-
-// DC -25000 counts, a bounded random walk (piecewise-linear between random knots every 64 and
-// 1024 frames), a 10 Hz sinusoid of 200 counts and white noise, clipped to int16; about one
-// sample in 65536 is a -32768 saturation.
-__global__ __launch_bounds__(256) void synth_kernel(int16_t* __restrict__ dst, int64_t n_frames,
-                                                    int ct, uint64_t seed) {
-  const int64_t total = n_frames * ct;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t t = idx / ct;
-    const int c = (int)(idx - t * ct);
-    const uint64_t ck = (uint64_t)c << 48;
-    const int64_t k1 = t >> 6, k2 = t >> 10;
-    const float f1 = (float)(t & 63) * (1.0f / 64.0f), f2 = (float)(t & 1023) * (1.0f / 1024.0f);
-    const float w1 = unit_noise(seed, ck | (uint64_t)(2 * k1)) * (1.0f - f1) +
-                     unit_noise(seed, ck | (uint64_t)(2 * k1 + 2)) * f1;
-    const float w2 = unit_noise(seed + 1, ck | (uint64_t)k2) * (1.0f - f2) +
-                     unit_noise(seed + 1, ck | (uint64_t)(k2 + 1)) * f2;
-    const float sine = 200.0f * __sinf(6.2831853f * 10.0f * (float)(t % 1000) / 1000.0f + (float)c);
-    const float noise = 40.0f * unit_noise(seed + 2, (uint64_t)idx);
-    float v = -25000.0f + 1500.0f * w1 + 4000.0f * w2 + sine + noise;
-    if (unit_noise(seed + 3, (uint64_t)idx) < -0.99997f) v = -40000.0f;
-    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
-    dst[idx] = (int16_t)__float2int_rn(v);
   }
 }
 
@@ -1199,32 +797,28 @@ static hipError_t cut_features_impl(hipStream_t st, const void* raw, int fmt, in
   const int fbytes = ct * (fmt == 0 ? 2 : 4);
   const float* bs = (const float*)scratch;
   const Guard g = fast ? guard : Guard{nullptr, nullptr, nullptr};
-  if (fmt == 0 && ct == 3 && C == 3) {  // the reference's file: eight epochs per workgroup
-    const dim3 g8((unsigned)((n + dev::kCfEpochs - 1) / dev::kCfEpochs));
-    if (fast)
-      hipLaunchKernelGGL((dev::cut_features_c3_kernel<true, true, E>), g8, block, 0, st,
+  auto launch = [&](auto fa) {  // fa: `fast` as a type, the kernels' FAST
+    constexpr bool FA = decltype(fa)::value;
+    if (fmt == 0 && ct == 3 && C == 3) {  // the reference's file: eight epochs per workgroup
+      const dim3 g8((unsigned)((n + dev::kCfEpochs - 1) / dev::kCfEpochs));
+      hipLaunchKernelGGL((dev::cut_features_c3_kernel<FA, true, E>), g8, block, 0, st,
                          (const int16_t*)raw, n_frames, sel, pos, bs, n, out, feat, g);
-    else
-      hipLaunchKernelGGL((dev::cut_features_c3_kernel<false, true, E>), g8, block, 0, st,
-                         (const int16_t*)raw, n_frames, sel, pos, bs, n, out, feat, g);
-  } else if (fbytes % 4 != 0) {  // int16, packed frames
-    const size_t lds = dev::staged_features_lds((size_t)dev::kPost * fbytes + 8, C);
-    if (fast)
-      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, true, E>), grid, block, lds, st,
+    } else if (fbytes % 4 != 0) {  // int16, packed frames
+      const size_t lds = dev::staged_features_lds((size_t)dev::kPost * fbytes + 8, C);
+      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, FA, E>), grid, block, lds, st,
                          (const int16_t*)raw, n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g);
-    else
-      hipLaunchKernelGGL((dev::cut_write_lds_packed_kernel<true, false, E>), grid, block, lds, st,
-                         (const int16_t*)raw, n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g);
-  } else {
-    const int fs_bytes = (fbytes / 4 + 1) * 4;
-    const size_t lds = dev::staged_features_lds((size_t)dev::kPost * fs_bytes, C);
-#define EEGFX_CF(T, FA)                                                                           \
-    hipLaunchKernelGGL((dev::cut_write_lds_kernel<T, true, FA, E>), grid, block, lds, st, (const T*)raw, \
-                       n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g)
-    if (fmt == 0) { if (fast) EEGFX_CF(int16_t, true); else EEGFX_CF(int16_t, false); }
-    else { if (fast) EEGFX_CF(float, true); else EEGFX_CF(float, false); }
-#undef EEGFX_CF
-  }
+    } else {
+      const int fs_bytes = (fbytes / 4 + 1) * 4;
+      const size_t lds = dev::staged_features_lds((size_t)dev::kPost * fs_bytes, C);
+      if (fmt == 0)
+        hipLaunchKernelGGL((dev::cut_write_lds_kernel<int16_t, true, FA, E>), grid, block, lds, st,
+                           (const int16_t*)raw, n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g);
+      else
+        hipLaunchKernelGGL((dev::cut_write_lds_kernel<float, true, FA, E>), grid, block, lds, st,
+                           (const float*)raw, n_frames, ct, sel, C, pos, bs, out, dev::kPost, feat, g);
+    }
+  };
+  if (fast) launch(std::true_type{}); else launch(std::false_type{});
   return hipGetLastError();
 }
 hipError_t launch_cut_features(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
@@ -1269,39 +863,6 @@ bool cut_features_supported(int fmt, int ct, int C, const void* raw, const float
   return cut_features_fit(fmt, ct, C, raw, out, 4, feat);
 }
 
-template <typename E>
-static hipError_t features_from_epochs_impl(hipStream_t st, const E* ep, int64_t n, int C, int skip,
-                                            int nfeat, bool fast, double* out, int row_stride,
-                                            const Guard& guard) {
-  if (n == 0) return hipSuccess;
-  // The rows stay in LDS while the workgroup (33 KB of windows + 8 rows) still fits three times
-  // per CU (C <= 20 at 16 features); wider rows go through `out`, which keeps four per CU.
-  // Measured (profiles/r04q/, fma / EXACT): C = 24 rows in LDS 2.86 / 3.52 ms, through `out`
-  // 2.61 / 2.77 ms; C = 32 2.88 / 3.53 vs 2.82 / 2.96 ms; C = 16 2.40 / 2.54 vs 2.57 / 2.72 ms.
-  const size_t lds_rows = dev::kFeWinBytes + sizeof(double) * (8 * (size_t)C * nfeat + 8);
-  const bool rows_out = 3 * lds_rows > 160 * 1024;
-  const size_t smem = sizeof(double) * (rows_out ? 8 * 16 + 8 : 8 * (size_t)C * nfeat + 8);
-  dim3 grid((unsigned)((n + 7) / 8)), block(64);
-  const Guard none{nullptr, nullptr, nullptr};
-#define EEGFX_FFE(FA, RO)                                                                         \
-  hipLaunchKernelGGL((dev::features_from_epochs_kernel<FA, RO, E>), grid, block, smem, st, ep, n, \
-                     C, skip, nfeat, row_stride, out, FA ? guard : none)
-  if (fast) { if (rows_out) EEGFX_FFE(true, true); else EEGFX_FFE(true, false); }
-  else { if (rows_out) EEGFX_FFE(false, true); else EEGFX_FFE(false, false); }
-#undef EEGFX_FFE
-  return hipGetLastError();
-}
-hipError_t launch_features_from_epochs(hipStream_t st, const double* ep, int64_t n, int C, int skip,
-                                       int nfeat, bool fast, double* out, int row_stride,
-                                       const Guard& guard) {
-  return features_from_epochs_impl(st, ep, n, C, skip, nfeat, fast, out, row_stride, guard);
-}
-hipError_t launch_features_from_epochs(hipStream_t st, const float* ep, int64_t n, int C, int skip,
-                                       int nfeat, bool fast, double* out, int row_stride,
-                                       const Guard& guard) {
-  return features_from_epochs_impl(st, ep, n, C, skip, nfeat, fast, out, row_stride, guard);
-}
-
 // getData() as float32 (eegfx_odp_get_data_f32): the provider's resident double epochs are
 // widened fp32 values, so the narrowing is exact.  Both buffers are device allocations (16-byte
 // aligned): four doubles in, one 16-byte store out per lane; the last count % 4 by single lanes.
@@ -1324,33 +885,6 @@ hipError_t launch_narrow_epochs(hipStream_t st, const double* in, float* out, in
   blocks = blocks < 1 ? 1 : blocks > 65536 ? 65536 : blocks;
   hipLaunchKernelGGL(dev::narrow_epochs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out,
                      count);
-  return hipGetLastError();
-}
-
-bool features_small_supported(int C) { return C >= 1 && C <= dev::kSmallMaxC; }
-
-hipError_t launch_features_mailbox(hipStream_t st, MailboxCmd* mb, uint64_t idle_ticks,
-                                   uint32_t gen) {
-  hipLaunchKernelGGL(dev::features_mailbox_kernel, dim3(1), dim3(256), 0, st, mb, idle_ticks, gen);
-  return hipGetLastError();
-}
-
-hipError_t launch_features_small(hipStream_t st, const double* rows, int64_t n, int C, int nfeat,
-                                 double* out) {
-  if (n == 0) return hipSuccess;
-  if (!features_small_supported(C)) return hipErrorNotSupported;
-  hipLaunchKernelGGL(dev::features_small_kernel, dim3((unsigned)n), dim3(256), 0, st, rows, C,
-                     nfeat, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_synth(hipStream_t st, int16_t* dst, int64_t n_frames, int ct, uint64_t seed) {
-  const int64_t total = n_frames * ct;
-  if (total == 0) return hipSuccess;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(dev::synth_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, n_frames,
-                     ct, seed);
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// launch.h -- host-side launchers of the gfx950 kernels (kernels.hip, fused.hip, wide.hip,
-// pyramid.hip).
+// launch.h -- host-side launchers of the gfx950 kernels (cut.hip, extract.hip, small.hip,
+// synth.hip, fused.hip, wide.hip, pyramid.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -30,7 +30,7 @@ hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n
 hipError_t launch_cut_epochs(hipStream_t st, const void* raw, int fmt, int64_t n_frames, int ct,
                              const ChanSel& sel, int C, const int64_t* pos, int64_t n,
                              float* out, void* scratch, int* err);
-// The one-pass getData + features (kernels.hip staged_features): baselines, then one workgroup
+// The one-pass getData + features (cut.hip staged_features): baselines, then one workgroup
 // per epoch writes the epoch's rows to `out` (double[n][C][750]) and its normalised dwt-8 row to
 // `feat` (double[n][16 C]) from the same LDS-staged frames.  hipErrorNotSupported when the layout
 // does not fit (cut_features_supported): the caller cuts, then extracts from the rows.
@@ -61,7 +61,7 @@ hipError_t launch_features_from_epochs(hipStream_t st, const float* ep, int64_t 
                                        const Guard& guard);
 // double[count] -> float[count] on the device (eegfx_odp_get_data_f32); 16-byte-aligned buffers
 hipError_t launch_narrow_epochs(hipStream_t st, const double* in, float* out, int64_t count);
-// Small host batches (kernels.hip features_small_kernel): rows = n x C x 512 packed window rows,
+// Small host batches (small.hip features_small_kernel): rows = n x C x 512 packed window rows,
 // one workgroup per epoch, C <= 16; rows / out may be device pointers of mapped pinned memory.
 bool features_small_supported(int C);
 // guard.total counts the rows the kernel recomputed under EXACT (guard.h); count/list unused.

@@ -91,7 +91,7 @@ __device__ __forceinline__ void pyramid_rescale(double* __restrict__ o, int ne, 
   }
 }
 
-// Window rows in LDS as features_from_epochs_kernel stages them (kernels.hip): segment s of
+// Window rows in LDS as features_from_epochs_kernel stages them (extract.hip): segment s of
 // signal g at g * kPyWin + s * kPySeg doubles, 65 and 520 doubles, so a half-wave's reads of one
 // sample index fall on 64 distinct banks.
 constexpr int kPySeg = kSegLen + 1;

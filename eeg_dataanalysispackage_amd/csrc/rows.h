@@ -1,6 +1,6 @@
 // rows.h -- normalisation and store of the feature rows of an 8-epoch sub-tile, shared by the
 // fused window kernel (fused.hip: its EXACT rows; its fma rows leave from registers) and the
-// one-pass getData + features kernels (kernels.hip: both numerics).
+// one-pass getData + features kernels (cut.hip: both numerics).
 #pragma once
 
 #include <hip/hip_runtime.h>

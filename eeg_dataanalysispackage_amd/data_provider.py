@@ -6,7 +6,7 @@ formats (``[info.txt]`` or ``[file.eeg, guessed, ...]``), the same per-file skip
 same error behaviour: ``loadData`` never raises -- it logs the fatal error, keeps what was loaded
 and exposes the message as ``last_error``.  Paths are local files (the reference reads HDFS).
 
-Decode, epoch cut and baseline correction run on the GPU (csrc/kernels.hip); the epochs stay
+Decode, epoch cut and baseline correction run on the GPU (csrc/cut.hip); the epochs stay
 resident in HBM and ``getData()`` copies them back.
 
 ``OffLineDataProvider(args, contexts=[...])`` shards ``loadData()`` over several contexts (any mix

@@ -1,6 +1,6 @@
 """Where the epoch kernels are tested at the first and the last layout of every dispatch bucket
-(DESIGN.md section 10.6): raw recording -> baselines -> epochs -> dwt-8 rows (kernels.hip, wide.hip,
-fused.hip, guard.hip, routed by routes.cpp).  Which kernel a call takes is decided by host-side
+(DESIGN.md section 10.6): raw recording -> baselines -> epochs -> dwt-8 rows (cut.hip, extract.hip,
+small.hip, wide.hip, fused.hip, guard.hip, routed by routes.cpp).  Which kernel a call takes is decided by host-side
 predicates on (sample type, channels in the file ct, selected channels C), the output's alignment
 and the marker spacing, most of them an LDS-size formula compared with a limit.  tests/
 refusal_cases.py restates most of those predicates; this module imports them, restates the three
@@ -21,9 +21,9 @@ from refusal_cases import (INT16, FLOAT32, PRE, POST, baseline_any_tile, cut_wri
 
 # ---- the restatements refusal_cases.py lacks ------------------------------------------------------
 WIDE_TWO_MAX = 32 * 1024           # wide.hip launch_window_wide_kernels: two epochs a workgroup
-FE_WIN_BYTES = 8 * 8 * 8 * 65      # kernels.hip kFeWinBytes: 8 windows of 8 segments of 65 doubles
-FE_CU_LDS = 160 * 1024             # kernels.hip features_from_epochs_impl: 3 workgroups a CU
-SMALL_MAX_C = 16                   # kernels.hip kSmallMaxC
+FE_WIN_BYTES = 8 * 8 * 8 * 65      # extract.hip kFeWinBytes: 8 windows of 8 segments of 65 doubles
+FE_CU_LDS = 160 * 1024             # extract.hip features_from_epochs_impl: 3 workgroups a CU
+SMALL_MAX_C = 16                   # small.hip kSmallMaxC
 ZERO_COPY_BYTES = 768 << 10        # api.cpp kZeroCopyBytes: the small host batches
 WIN = 512                          # dwt8.h kWin
 GUARD_GRID, GUARD_BLOCK = 16, 128  # guard.hip kGuardGrid, kGuardBlock
@@ -48,7 +48,7 @@ LIMIT = {
 
 
 def cut_chunk_frames(frame_bytes_, slack):
-    """kernels.hip cut_chunk_frames: (frames a chunk, chunks) of the staged write passes."""
+    """cut.hip cut_chunk_frames: (frames a chunk, chunks) of the staged write passes."""
     nch = 1
     while True:
         nfc = ((POST + nch - 1) // nch + 1) & ~1
@@ -85,7 +85,7 @@ def features_kernels(fmt, ct, C, out_aligned=True):
 
 
 def rows_out(C, nfeat):
-    """kernels.hip features_from_epochs_impl: the rows leave through `out`, not LDS."""
+    """extract.hip features_from_epochs_impl: the rows leave through `out`, not LDS."""
     return 3 * (FE_WIN_BYTES + 8 * (8 * C * nfeat + 8)) > FE_CU_LDS
 
 
@@ -98,7 +98,7 @@ def features_small_supported(C):
 
 
 def stage_rule(fmt, ct, C):
-    """kernels.hip cut_epochs_impl `stage`: staged frames at most twice the rows written."""
+    """cut.hip cut_epochs_impl `stage`: staged frames at most twice the rows written."""
     return POST * frame_bytes(fmt, ct) <= 2 * 6000 * C
 
 

@@ -27,9 +27,9 @@ ANY_LANES = 256                    # wide.hip baseline_any_tile: EB = 256 / C
 ANY_LDS_TARGET = 56 * 1024         # ... lowered while EB staged runs exceed 56 KB
 ANY_LDS_MAX = 64 * 1024            # wide.hip baseline_any_supported
 WIDE_LDS_MAX = 64 * 1024           # wide.hip wide_supported
-CUT_PAIRS = 5                      # kernels.hip kCutPairs: cut_write_small_kernel's pairs a thread
-CF_EPOCHS = 8                      # kernels.hip kCfEpochs: epochs a workgroup of the c3 kernel
-CUT_LDS_MAX = 64 * 1024            # kernels.hip EEGFX_CUT_LDS_MAX
+CUT_PAIRS = 5                      # cut.hip kCutPairs: cut_write_small_kernel's pairs a thread
+CF_EPOCHS = 8                      # cut.hip kCfEpochs: epochs a workgroup of the c3 kernel
+CUT_LDS_MAX = 64 * 1024            # cut.hip EEGFX_CUT_LDS_MAX
 
 # ---- the capped grid-stride loops -----------------------------------------------------------------
 THREADS = 256
@@ -99,7 +99,7 @@ def features_route(fmt, ct, C):
 
 
 def cut_writer(fmt, ct, C, out_aligned=True):
-    """kernels.hip cut_epochs_impl for a dword-aligned recording: (checker, tile, writer).
+    """cut.hip cut_epochs_impl for a dword-aligned recording: (checker, tile, writer).
     out_aligned: float epochs always; double epochs when `out` lies on a 16-byte boundary."""
     chk = checker(fmt, ct, C) if out_aligned else None
     if chk is None:
@@ -121,7 +121,7 @@ def staged_features_lds(stage_bytes, C):
 
 
 def one_pass_writer(fmt, ct, C):
-    """kernels.hip cut_features_fit / cut_features_impl for aligned buffers: (checker, tile,
+    """cut.hip cut_features_fit / cut_features_impl for aligned buffers: (checker, tile,
     writer) of the one-pass epochs + features, None where the entry cuts and then extracts."""
     fb = frame_bytes(fmt, ct)
     if not 1 <= C <= MAX_CHANNELS or (fb % 4 != 0 and fmt != INT16) or checker(fmt, ct, C) is None:
@@ -135,16 +135,18 @@ def one_pass_writer(fmt, ct, C):
                                   else "cut_write_lds_kernel",)
 
 
-# The nine copies of "an invalid position is cut as pos = 100", by the kernel that holds each
-# (file:line when this table was written), and the two checkers, which clamp as well.
+# The nine kernels that cut "an invalid position as pos = 100", by the file that holds each, and
+# the two checkers, which clamp as well.  cut.hip's six kernels call its one cut_position();
+# the others carry a copy of the expression each.
 CLAMPS = {
-    "cut_epochs_kernel": "kernels.hip:92", "cut_write_kernel": "kernels.hip:128",
-    "cut_write_small_kernel": "kernels.hip:172", "cut_features_c3_kernel": "kernels.hip:373",
-    "cut_write_lds_kernel": "kernels.hip:534", "cut_write_lds_packed_kernel": "kernels.hip:636",
-    "window_wide_kernel": "wide.hip:179", "window_c32_kernel": "wide.hip:326",
-    "exact_rows_kernel": "guard.hip:49",
+    "cut_epochs_kernel": "cut.hip", "cut_write_kernel": "cut.hip",
+    "cut_write_small_kernel": "cut.hip", "cut_features_c3_kernel": "cut.hip",
+    "cut_write_lds_kernel": "cut.hip", "cut_write_lds_packed_kernel": "cut.hip",
+    "window_wide_kernel": "wide.hip", "window_c32_kernel": "wide.hip",
+    "exact_rows_kernel": "guard.hip",
 }
-CLAMPS_PER_FILE = {"kernels.hip": 6, "wide.hip": 3, "guard.hip": 1, "fused.hip": 1}
+# the clamps a file holds: cut.hip's are calls of cut_position(), the others copies
+CLAMPS_PER_FILE = {"cut.hip": 6, "wide.hip": 3, "guard.hip": 1, "fused.hip": 1}
 
 
 # ---- layouts --------------------------------------------------------------------------------------

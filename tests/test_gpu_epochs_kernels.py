@@ -1,6 +1,7 @@
-"""The materialised-epoch kernels on the device (kernels.hip): features_from_epochs_kernel (batched
+"""The materialised-epoch kernels on the device: features_from_epochs_kernel (extract.hip; batched
 WaveletTransform.extractFeatures on double[n][C][750], WaveletTransform.java:107-141) and the
-getData() write passes cut_write_small_kernel / cut_write_kernel (OffLineDataProvider.java:216-233).
+getData() write passes cut_write_small_kernel / cut_write_kernel (cut.hip;
+OffLineDataProvider.java:216-233).
 
 The batch extractor stages eight windows per channel through LDS and, under fma numerics, runs the
 collapsed four-point filter on the doubles; its feature rows sit in dynamic LDS (8 x 16C doubles)

@@ -1,6 +1,6 @@
 """The epoch kernels at the first and the last layout of every dispatch bucket: raw recording ->
-baselines -> epochs -> dwt-8 rows (kernels.hip, wide.hip, fused.hip, guard.hip) at the layouts
-tests/layout_cases.py names.  tests/test_layout_cases.py has shown off
+baselines -> epochs -> dwt-8 rows (cut.hip, extract.hip, small.hip, wide.hip, fused.hip,
+guard.hip) at the layouts tests/layout_cases.py names.  tests/test_layout_cases.py has shown off
 the GPU that each case takes the kernels, the chunk count and the LDS bytes it is named for --
 among them the first launches above 64 KB of static + dynamic LDS -- and that the two layouts of
 every edge pair take different kernels; here every case runs, and must

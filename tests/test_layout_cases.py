@@ -22,7 +22,7 @@ def ids(cases):
 
 # ---- the restated rules are the sources' ----------------------------------------------------------
 def test_cut_chunk_frames_is_the_sources():
-    k = source("kernels.hip")
+    k = source("cut.hip")
     chunk = body(k, "static int cut_chunk_frames(")
     assert "for (int nch = 1;; ++nch) {" in chunk
     assert "const int nfc = ((dev::kPost + nch - 1) / nch + 1) & ~1;" in chunk
@@ -79,7 +79,7 @@ def test_the_two_rule_and_the_wide_launch_are_the_sources():
 
 
 def test_rows_out_and_the_small_batches_are_the_sources():
-    k = source("kernels.hip")
+    k = source("extract.hip")
     impl = body(k, "static hipError_t features_from_epochs_impl(")
     assert "const size_t lds_rows = dev::kFeWinBytes + sizeof(double) * (8 * (size_t)C * nfeat + 8);" in impl
     assert ints(r"const bool rows_out = 3 \* lds_rows > (\d+) \* 1024;", impl) == (L.FE_CU_LDS // 1024,)
@@ -92,8 +92,9 @@ def test_rows_out_and_the_small_batches_are_the_sources():
     assert "constexpr int kSegLen = kWin / kLanesPerSignal;" in dwt
     assert ints(r"constexpr int kLanesPerSignal = (\d+);", dwt) == (8,)
     assert L.FE_WIN_BYTES == 8 * 8 * 8 * (L.WIN // 8 + 1) == 33280
-    assert ints(r"constexpr int kSmallMaxC = (\d+);", k) == (L.SMALL_MAX_C,)
-    assert "return C >= 1 && C <= dev::kSmallMaxC;" in body(k, "bool features_small_supported(")
+    small = source("small.hip")
+    assert ints(r"constexpr int kSmallMaxC = (\d+);", small) == (L.SMALL_MAX_C,)
+    assert "return C >= 1 && C <= dev::kSmallMaxC;" in body(small, "bool features_small_supported(")
     api = source("api.cpp")
     assert ints(r"constexpr size_t kZeroCopyBytes = \(size_t\)(\d+) << (\d+);", api) == (768, 10)
     assert "(size_t)n * C * row_w <= kZeroCopyBytes && features_small_supported(C) &&" in api
@@ -107,7 +108,7 @@ def test_static_shared_declarations_are_the_ones_counted():
     def shared(text):
         return sorted(re.findall(r"^\s*(?:extern )?__shared__ (.*);", text, re.M))
 
-    wide, k = source("wide.hip"), source("kernels.hip")
+    wide, k = source("wide.hip"), source("cut.hip")
     assert shared(body(wide, "void baseline_any_kernel(")) == \
         ["__attribute__((aligned(16))) uint8_t smem[]", "int64_t sB[256]"]
     assert shared(body(wide, "void window_wide_kernel(")) == \
@@ -116,7 +117,7 @@ def test_static_shared_declarations_are_the_ones_counted():
         assert shared(body(k, head)) == \
             ["__attribute__((aligned(16))) uint32_t stage[]", "float s_res[kMaxChannels], s_base[kMaxChannels]",
              "int s_col[kMaxChannels]"], head
-    assert shared(body(k, "void features_from_epochs_kernel(")) == \
+    assert shared(body(source("extract.hip"), "void features_from_epochs_kernel(")) == \
         ["__attribute__((aligned(16))) double fsmem[]", "__attribute__((aligned(16))) double win[8 * kFeWin]"]
     assert L.STATIC == {"baseline_any_kernel": 2048, "cut_write_lds_kernel": 768,
                         "cut_write_lds_packed_kernel": 768, "window_wide_kernel": 0,

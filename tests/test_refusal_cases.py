@@ -61,7 +61,7 @@ def test_baseline_any_tile_and_the_wide_bound():
 
 
 def test_writer_choice_constants():
-    k = source("kernels.hip")
+    k = source("cut.hip")
     assert ints(r"constexpr int kCutPairs = (\d+);", k) == (R.CUT_PAIRS,)
     assert ints(r"constexpr int kCfEpochs = (\d+);", k) == (R.CF_EPOCHS,)
     assert ints(r"#define EEGFX_CUT_LDS_MAX \((\d+) \* 1024\)", k) == (R.CUT_LDS_MAX // 1024,)
@@ -104,14 +104,24 @@ def test_grid_caps():
 
 
 def test_the_clamps_are_the_eleven_the_routes_are_written_for():
-    """Nine copies in the kernels that read a position again, two in the checkers.  A tenth copy
-    needs a route of its own in refusal_cases.ROUTES."""
+    """Nine clamps in the kernels that read a position again, two in the checkers.  A tenth
+    needs a route of its own in refusal_cases.ROUTES.  cut.hip writes the expression once, in
+    cut_position(), and each of its six kernels calls that; the other files hold copies."""
     clamp = re.compile(r"\? p0? : (?:\(int64_t\))?kPre")
+    cut = source("cut.hip")
     for name, want in R.CLAMPS_PER_FILE.items():
-        assert len(clamp.findall(source(name))) == want, name
+        if name == "cut.hip":
+            assert clamp.findall(cut) == clamp.findall(body(cut, "int64_t cut_position(")) \
+                == ["? p0 : kPre"]
+            assert len(re.findall(r"(?<!int64_t )cut_position\(", cut)) == want
+        else:
+            assert len(clamp.findall(source(name))) == want, name
+    callers = [k for k, f in R.CLAMPS.items() if f == "cut.hip"]
+    assert len(callers) == R.CLAMPS_PER_FILE["cut.hip"]
+    for kernel in callers:
+        assert body(cut, "void %s(" % kernel).count("cut_position(") == 1, kernel
     assert sum(R.CLAMPS_PER_FILE.values()) == len(R.CLAMPS) + 2
-    assert "if (threadIdx.x == 0 && !ok && err)" in \
-        body(source("kernels.hip"), "void cut_epochs_kernel(")
+    assert "if (threadIdx.x == 0 && !ok && err)" in body(cut, "void cut_epochs_kernel(")
 
 
 # ---- positions ------------------------------------------------------------------------------------

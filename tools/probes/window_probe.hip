@@ -33,7 +33,7 @@
 #endif
 #include FUSED_SRC
 #include WIDE_SRC
-#include "../../eeg_dataanalysispackage_amd/csrc/kernels.hip"
+#include "../../eeg_dataanalysispackage_amd/csrc/synth.hip"
 #include "../../eeg_dataanalysispackage_amd/csrc/guard.hip"
 
 int main() {
