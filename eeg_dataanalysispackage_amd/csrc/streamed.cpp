@@ -2,30 +2,10 @@
 // chunk buffers (BASELINE.json configs[4]).
 #include <algorithm>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "ctx.h"
-
-// Host copy into pinned staging, split over up to 8 threads (one thread tops out near 6 GB/s,
-// far below the ~57 GB/s host link it feeds).
-static void parallel_memcpy(void* dst, const void* src, size_t bytes) {
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const size_t nt = std::min<size_t>({8, hw, std::max<size_t>(1, bytes >> 23)});
-  if (nt <= 1) {
-    memcpy(dst, src, bytes);
-    return;
-  }
-  std::vector<std::thread> th;
-  const size_t per = (bytes / nt + 63) & ~(size_t)63;
-  for (size_t t = 0; t < nt; ++t) {
-    const size_t a = t * per;
-    if (a >= bytes) break;
-    const size_t len = std::min(per, bytes - a);
-    th.emplace_back([=] { memcpy((char*)dst + a, (const char*)src + a, len); });
-  }
-  for (auto& x : th) x.join();
-}
+#include "stream_plan.h"
 
 extern "C" {
 
@@ -47,7 +27,7 @@ int eegfx_process_recording_streamed(eegfx_ctx* ctx, const void* raw, int32_t fm
   return guarded([&] {
     // the raw entries' ladder (api.cpp), with the chunk size checked ahead of the selection
     check_raw_head(ctx, EEGFX_MEM_HOST, raw, fmt, n_frames, ct, pos, n, features);
-    constexpr int64_t kSpan = EEGFX_PRESTIMULUS + EEGFX_DWT8_SKIP + EEGFX_DWT8_EPOCH_SIZE;  // 787
+    constexpr int64_t kSpan = kStreamSpan;  // 787
     if (chunk_frames < kSpan)
       fail(EEGFX_EINVAL, "chunk_frames %lld < one epoch span (%lld)", (long long)chunk_frames,
            (long long)kSpan);
@@ -82,40 +62,14 @@ int eegfx_process_recording_streamed(eegfx_ctx* ctx, const void* raw, int32_t fm
                              ctx->stream));
     double* d_out = (double*)ctx->out.get(sizeof(double) * (size_t)(n * F));
     (void)ctx->fused.get(fused_scratch_bytes(n, C));  // every chunk's baselines fit: no realloc
-    // chunk buffers: 64 B front pad (the kernels round the first quad down by < 16 B) + data
-    // (rounded to 256 B so the second buffer is as aligned as the first: the kernels read
-    // 16-byte quads relative to `raw`)
-    const size_t cbytes = ((size_t)(chunk_frames * FB) + 128 + 255) & ~(size_t)255;
-    // Chunk sizes ramp up (c/4, c/2, then c) and down (about half of what remains, not below
-    // c/4) so that the first upload and the last download -- the parts of a call that nothing
-    // overlaps -- stay short.
-    const int64_t last = spos[n - 1] - EEGFX_PRESTIMULUS + kSpan;
-    auto chunk_at = [&](int64_t k, int64_t lo) {
-      int64_t c = k < 2 ? chunk_frames >> (2 - k) : chunk_frames;
-      const int64_t rest = last - lo;
-      if (rest < 2 * chunk_frames) c = std::min(c, (rest + 1) / 2);
-      return std::min(chunk_frames, std::max(c, std::max(chunk_frames / 4, 2 * kSpan)));
-    };
-    struct Chunk {
-      int64_t i, j, lo, hi;  // epochs [i, j), frames [lo, hi)
-    };
-    std::vector<Chunk> plan;
-    for (int64_t i = 0; i < n;) {
-      const int64_t lo = spos[i] - EEGFX_PRESTIMULUS;
-      const int64_t hi = std::min(lo + chunk_at((int64_t)plan.size(), lo), n_frames);
-      // the epochs whose span [pos-100, pos+687) ends by hi (all of them at the recording end):
-      // a prefix of the sorted positions, found by bisection (a linear scan of configs[4]'s 576k
-      // positions delayed the first upload by ~150 us)
-      const int64_t j =
-          hi == n_frames ? n
-                         : std::upper_bound(spos + i, spos + n, hi + EEGFX_PRESTIMULUS - kSpan) - spos;
-      plan.push_back({i, j, lo, hi});
-      i = j;
-    }
+    // the chunks, and one buffer size for all of them (stream_plan.h; a chunk_frames beyond what
+    // the recording can use gives one chunk, sized by the recording)
+    const std::vector<StreamChunk> plan = stream_plan(spos, n, n_frames, chunk_frames);
+    const size_t cbytes = stream_buffer_bytes(plan, FB);
     // A ring of 4 device chunk buffers (fewer for fewer chunks).  One buffer per chunk (the whole
     // 346 MB recording in HBM, no upload ever waiting for an earlier chunk's kernels) measured the
     // same: 7.16-7.18 against 7.13-7.18 ms (profiles/r06/stream_ring_ab.log).
-    const size_t R = std::min<size_t>(plan.size(), 4);
+    const size_t R = stream_ring(plan.size());
     uint8_t* dbuf = (uint8_t*)ctx->raw.get(R * cbytes);
     hipPointerAttribute_t attr;
     const bool pinned = hipPointerGetAttributes(&attr, raw) == hipSuccess &&
@@ -132,17 +86,18 @@ int eegfx_process_recording_streamed(eegfx_ctx* ctx, const void* raw, int32_t fm
       }
       ctx->drain();  // d_pos uploaded; buffers idle
       for (size_t k = 0; k < plan.size(); ++k) {
-        const size_t b = k % R;
-        const int64_t i = plan[k].i, j = plan[k].j, lo = plan[k].lo, hi = plan[k].hi;
-        const int64_t Lb = (lo * FB) & ~(int64_t)15, Hb = hi * FB;
-        const size_t bytes = Hb > Lb ? (size_t)(Hb - Lb) : 0;
+        const size_t b = stream_slot(k, R), st = stream_staging(k);
+        const int64_t i = plan[k].i, j = plan[k].j, hi = plan[k].hi;
+        const StreamBytes cb = stream_chunk_bytes(plan[k], FB);
+        const int64_t Lb = cb.Lb;
+        const size_t bytes = cb.bytes;
         uint8_t* dst = dbuf + (size_t)b * cbytes + 64;
         if (k >= R) HIP_CHECK(hipStreamWaitEvent(cs, done[b], 0));  // kernels of chunk k-R done
         const uint8_t* src = (const uint8_t*)raw + Lb;
-        if (!pinned) {  // two pinned staging buffers: staging k&1 is free once chunk k-2 uploaded
+        if (!pinned) {  // two pinned staging buffers: staging k % 2 is free once chunk k-2 uploaded
           if (k >= 2) HIP_CHECK(hipEventSynchronize(copied[(k - 2) % R]));
-          if (bytes) parallel_memcpy(pin[k & 1], src, bytes);
-          src = (const uint8_t*)pin[k & 1];
+          if (bytes) parallel_memcpy(pin[st], src, bytes);
+          src = (const uint8_t*)pin[st];
         }
         if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
         HIP_CHECK(hipEventRecord(copied[b], cs));

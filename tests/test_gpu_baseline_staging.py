@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import eeg_dataanalysispackage_amd as fx
+import stream_cases as S
 from eeg_dataanalysispackage_amd import _lib
 from oracle import oracle
 
@@ -144,15 +145,35 @@ def test_permuted_channels_with_their_own_resolutions(ctxs, recording, cols):
 
 
 # ---- the streamed path --------------------------------------------------------------------------
+def with_seams(pos, n_frames, chunk_frames, seams=6):
+    """pos and, for the first chunks of the restated plan (tests/stream_cases.py), an epoch at the
+    last position that still fits the chunk and one a frame later, which opens the next chunk.
+    Both lie below the highest position, so no earlier chunk moves."""
+    pos = sorted(int(p) for p in pos)
+    for k in range(seams):
+        ch = S.plan(pos, n_frames, chunk_frames)[k]
+        assert ch.hi < n_frames and ch.hi - S.TAIL + 1 < pos[-1]
+        pos = sorted(pos + [ch.hi - S.TAIL, ch.hi - S.TAIL + 1])
+    chunks = S.plan(pos, n_frames, chunk_frames)
+    for a, b in zip(chunks[:seams], chunks[1:]):
+        assert pos[a.j - 1] == a.hi - S.TAIL and pos[b.i] == a.hi - S.TAIL + 1 == b.lo + S.PRE
+    return np.array(pos, dtype=np.int64)
+
+
 @pytest.mark.parametrize("chunk_frames", [787, 1000])
 def test_streamed_chunks_equal_the_resident_call(ctxs, chunk_frames):
-    """A 5,000-frame host recording streamed in chunks: runs start at, end at and straddle every
-    chunk boundary, the kernels reading through each chunk's own pointer and byte count."""
+    """A 5,000-frame host recording streamed in chunks, the kernels reading through each chunk's
+    own pointer and byte count.  Runs start at, end at and straddle every multiple of
+    chunk_frames; the plan puts no chunk boundary there (a chunk starts at the first unprocessed
+    epoch's pos - 100), so the first six seams of the plan itself are added: an epoch that ends
+    exactly at its chunk's last frame and one a frame later.  tests/test_gpu_streamed_seams.py
+    has the seams case by case."""
     raw = synth_raw(41, 5000)
     edges = np.arange(chunk_frames, 5000, chunk_frames)
     near = np.concatenate([edges + d for d in (-1, 0, 1, 99, 100, 101)])
     pos = np.concatenate([np.arange(100, 5101, 37), near[(near >= 100) & (near <= 5100)]])
     pos = pos.astype(np.int64)
+    pos = np.concatenate([pos, np.setdiff1d(with_seams(pos, 5000, chunk_frames), pos)])
     want = oracle.process_recording(raw, COLS, RES, pos)
     for c, assert_close in zip(ctxs, (assert_exact, assert_fma)):
         resident = c.process_recording(raw, 3, COLS, RES, pos)
