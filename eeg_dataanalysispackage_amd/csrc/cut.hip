@@ -247,8 +247,9 @@ __global__ __launch_bounds__(256) void cut_write_small_kernel(
 // bank runs on them there -- lane = (channel, segment), 8 lanes per signal, 32 signals per pass
 // of the 4 waves (C <= 64: at most two passes) -- instead of a second pass that re-reads the
 // 12 KB of window rows from HBM.  smp(f, col): the staged raw sample of post-stimulus frame f;
-// gsmp(f, col): the same sample from the recording (both zero past its end).  The decode, filter
-// banks, normalisation and the fma guard are those of the fused kernels.  The feature row and the
+// gsmp(f, col): the same sample from the recording (both zero past its end; guard.h Recording).
+// The decode, filter banks, normalisation and the fma guard are those of the fused kernels (the
+// shared pieces of guard.h and dwt8.h).  The feature row and the
 // guard's rare-path scratch alias the staged frames once every wave is done with them (a barrier),
 // so the LDS stays that of the plain write pass: configs[3]'s 51 KB, three workgroups per CU.
 template <bool FAST, bool MEASURE, typename Smp, typename GSmp>
@@ -268,23 +269,12 @@ __device__ __forceinline__ void staged_features(Smp smp, GSmp gsmp, const int* s
     const int cc = valid ? c : 0;
     const int col = s_col[cc];
     const float r = s_res[cc], b = s_base[cc];
-    auto own = [&](int k) { return smp(175 + kSegLen * s + k, col); };
+    float ym = 0.0f;
+    signal_cascade<FAST, FAST && MEASURE>([&](int k) { return smp(175 + kSegLen * s + k, col); },
+                                          r, b, lane & ~7, s, a6v[pass], d6v[pass], &ym);
     if constexpr (FAST) {
-      float ym = 0.0f;
-      dwt8_collapsed_cascade<MEASURE>(own, r, b, lane & ~7, s, a6v[pass], d6v[pass], &ym);
-      double x2;
-      if constexpr (MEASURE) {
-        const double X = (double)group8_max(ym);
-        x2 = X * X;
-      } else {
-        x2 = guard_x2_int16(r, b);
-      }
+      const double x2 = signal_x2<MEASURE>(ym, r, b);
       if (valid && s == 0) gx[c] = x2;
-    } else {
-      double a1[40];
-      level1_exact(own, r, b, lane & ~7, s, a1);
-      halo<32, true>(a1, nullptr, lane & ~7, s);
-      dwt8_levels2to6<false, true>(a1, nullptr, lane & ~7, s, a6v[pass], d6v[pass]);
     }
   }
   __syncthreads();  // every wave is done with the staged frames: the row may overwrite them
@@ -303,25 +293,20 @@ __device__ __forceinline__ void staged_features(Smp smp, GSmp gsmp, const int* s
     if constexpr (FAST) {
       double acc = 0.0;
       for (int i = lane; i < F; i += 64) acc = __builtin_fma(feat[i], feat[i], acc);
-      double sx = lane < C ? gx[lane] : 0.0;  // C <= 64
-      for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_xor(acc, off, 64);
-        sx += __shfl_xor(sx, off, 64);
-      }
-      bool fails = guard.total && guard_fails(acc, kGuardK2Collapsed, sx);  // wave-uniform
-      if (!MEASURE && fails) {  // int16: the second stage, the row's measured max |x|
-        if (lane == 0) guard_count_rechecked(guard, 1);
-        fails = guard_fails(acc, kGuardK2Collapsed,
-                            guard_measured_x2_wave(
-                                [&](int c, int k) { return (int)gsmp(175 + k, s_col[c]); },
-                                [&](int c, float v) {
-                                  float y = v * s_res[c];
-                                  y = y - s_base[c];
-                                  return (double)y;
-                                },
-                                C, lane));
-      } else if (fails && lane == 0) {
-        guard_count_rechecked(guard, 1);  // float32: the first test is the measured one
+      const double sx = lane < C ? gx[lane] : 0.0;  // C <= 64
+      bool fails;  // wave-uniform (guard.h guard_row_fails_wave)
+      if constexpr (!MEASURE) {  // int16: the second stage, the row's measured max |x|
+        fails = guard_row_fails_wave(
+            acc, sx, guard.total != nullptr,
+            [&] {
+              return guard_measured_x2_wave(
+                  [&](int c, int k) { return (int)gsmp(175 + k, s_col[c]); },
+                  [&](int c) { return s_res[c]; }, [&](int c) { return s_base[c]; }, C, lane);
+            },
+            guard, lane);
+      } else {  // float32: the first test is the measured one
+        fails = guard_row_fails_wave(acc, sx, guard.total != nullptr, GuardMeasuredFirst{}, guard,
+                                     lane);
       }
       if (lane == 0) {
         sh[0] = rsqrt_nr(acc);
@@ -340,9 +325,7 @@ __device__ __forceinline__ void staged_features(Smp smp, GSmp gsmp, const int* s
       if (w == 0) {
         dwt8_exact_row_wave(
             [&](int c, int k) {
-              float y = gsmp(175 + k, s_col[c]) * s_res[c];
-              y = y - s_base[c];
-              return (double)y;
+              return (double)decode_f32(gsmp(175 + k, s_col[c]), s_res[c], s_base[c]);
             },
             C, 16, feat + F, feat, lane);
         if (lane == 0) {
@@ -485,15 +468,8 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
     auto fetch = [&](int k) {
       return (float)own[3 * k + (k >= 17 ? 2 : (k == 16 && late16 ? 2 : 0))];
     };
-    if constexpr (FAST) {
-      dwt8_collapsed_cascade(fetch, r, b, lane & ~7, s, a6, d6);
-      if (s == 0) gx[el * C + c] = guard_x2_int16(r, b);
-    } else {
-      double a1[40];
-      level1_exact(fetch, r, b, lane & ~7, s, a1);
-      halo<32, true>(a1, nullptr, lane & ~7, s);
-      dwt8_levels2to6<false, true>(a1, nullptr, lane & ~7, s, a6, d6);
-    }
+    signal_cascade<FAST>(fetch, r, b, lane & ~7, s, a6, d6);
+    if (FAST && s == 0) gx[el * C + c] = signal_x2<false>(0.0f, r, b);
   }
   double* fb = (double*)stage;
   __syncthreads();  // every wave is done with the staged frames: the rows may overwrite them
@@ -505,21 +481,19 @@ __global__ __launch_bounds__(256) void cut_features_c3_kernel(
   if (w == 0) {
     // the guard's rare path: the row recomputed under EXACT from the recording, the LDS past the
     // 8 rows as scratch (the other waves are done)
+    const Recording<int16_t> rec{(const uint8_t*)raw, n_frames, CT};
     auto redo = [&](int e, double* row) {
       const int64_t f0 = sP[e] + 175;
       dwt8_exact_row_wave(
           [&](int cc, int k) {
-            const float v = f0 + k < n_frames ? (float)raw[(f0 + k) * CT + s_col[cc]] : 0.0f;
-            float y = v * s_res[cc];
-            y = y - s_base[e * C + cc];
-            return (double)y;
+            return rec.x(f0 + k, s_col[cc], s_res[cc], s_base[e * C + cc]);
           },
           C, 16, fb + kCfEpochs * F, row, lane);
     };
     // the guard's second stage: the row's measured max |x| per channel, from the recording
     auto recheck = [&](int e) {
-      return recheck_c3<FB, 1>((const uint8_t*)raw, n_frames, sel, (sP[e] + 175) * FB,
-                            s_base + e * C, nullptr, true, lane);
+      return recheck_c3<FB>((const uint8_t*)raw, n_frames, sel, (sP[e] + 175) * FB,
+                            s_base + e * C, lane);
     };
     normalise_store<F, FAST, C>(fb, norm, fout + e0 * F, ne, lane, gx, guard, redo,
                                 per_row_recheck(recheck));
@@ -631,15 +605,14 @@ __global__ __launch_bounds__(256) void cut_write_lds_kernel(
   }
   if constexpr (FEAT) {  // one chunk per epoch (launcher): the window frames are staged
     double* gx = (double*)((uint8_t*)stage + staged_features_lds((size_t)nf * FS * 4, C) - 64 * 8 - 16);
+    const Recording<T> rec{(const uint8_t*)raw, n_frames, ct};
     staged_features<FAST, !std::is_same<T, int16_t>::value>(
         [&](int f, int col) {
           if constexpr (sizeof(T) == 2) return (float)((const int16_t*)stage)[2 * f * FS + col];
           else return ((const float*)stage)[f * FS + col];
         },
-        [&](int f, int col) {
-          return g0 + f < n_frames ? (float)raw[(g0 + f) * ct + col] : 0.0f;
-        },
-        s_col, s_res, s_base, C, (double*)stage, gx, gx + 64, fout + e * 16 * C, guard, t);
+        [&](int f, int col) { return rec.sample(g0 + f, col); }, s_col, s_res, s_base, C,
+        (double*)stage, gx, gx + 64, fout + e * 16 * C, guard, t);
   }
 }
 
@@ -674,10 +647,11 @@ __global__ __launch_bounds__(256) void cut_write_lds_packed_kernel(
   });
   if constexpr (FEAT) {  // one chunk per epoch (launcher): the window frames are staged
     double* gx = (double*)((uint8_t*)stage + staged_features_lds((size_t)total * 4, C) - 64 * 8 - 16);
+    const Recording<int16_t> rec{(const uint8_t*)raw, n_frames, ct};
     staged_features<FAST, false>(
         [&](int f, int col) { return (float)h[f * ct + col]; },
-        [&](int f, int col) { return g0 + f < n_frames ? (float)raw[(g0 + f) * ct + col] : 0.0f; },
-        s_col, s_res, s_base, C, (double*)stage, gx, gx + 64, fout + e * 16 * C, guard, t);
+        [&](int f, int col) { return rec.sample(g0 + f, col); }, s_col, s_res, s_base, C,
+        (double*)stage, gx, gx + 64, fout + e * 16 * C, guard, t);
   }
 }
 

@@ -35,6 +35,7 @@
 #include <cstdint>
 
 #include "dwt8_taps.h"
+#include "guard.h"
 
 // FMA numerics' filter bank: levels 1-5 collapsed into one 280-tap filter (dwt8_collapsed_cascade)
 // or the level-by-level cascade with partial-sum halos (dwt8_fast_cascade; A/B builds only).
@@ -535,16 +536,52 @@ __device__ __forceinline__ void dwt8_collapsed_cascade(Fetch fetch, float r, flo
   if constexpr (TRACK) *ymax = m;
 }
 
-// The largest value of v over the 8 lanes of a signal group.
+// The largest value of v over the 8 lanes of a signal group.  The float form is for the
+// accumulators of max |x| (dwt8_collapsed_cascade's ymax): fmaxf keeps them non-negative and
+// never NaN, so the bit pattern orders like the value and the maximum is the three DPP steps of
+// group_max_u32 (guard.h) on the bits, no ds_bpermute.
 __device__ __forceinline__ float group8_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 1, 64));
-  v = fmaxf(v, __shfl_xor(v, 2, 64));
-  return fmaxf(v, __shfl_xor(v, 4, 64));
+  return __uint_as_float(group_max_u32<8>(__float_as_uint(v)));
 }
 __device__ __forceinline__ double group8_max(double v) {
   v = fmax(v, __shfl_xor(v, 1, 64));
   v = fmax(v, __shfl_xor(v, 2, 64));
   return fmax(v, __shfl_xor(v, 4, 64));
+}
+
+// The filter bank of one signal from fetch(k), raw sample k < 64 of the lane's slice, with the
+// decode fused in: a6[s] and d6[s] of the signal whose 8 lanes start at gbase.
+//   FAST (fma numerics): the collapsed filter; TRACK also returns the lane's max |x| in *ymax.
+//     Under !EEGFX_COLLAPSED (A/B builds) the level-by-level cascade with partial-sum halos,
+//     which cannot track: a tracking caller keeps the collapsed filter.
+//   EXACT: level 1 on the lane's own samples (the 8 halo samples as decoded doubles from lane
+//     s + 1), then value halos in the reference's order.
+template <bool FAST, bool TRACK = false, typename Fetch>
+__device__ __forceinline__ void signal_cascade(Fetch fetch, float r, float b, int gbase, int s,
+                                               double& a6, double& d6, float* ymax = nullptr) {
+  if constexpr (FAST) {
+    if constexpr (EEGFX_COLLAPSED || TRACK) {
+      dwt8_collapsed_cascade<TRACK>(fetch, r, b, gbase, s, a6, d6, ymax);
+    } else {
+      dwt8_fast_cascade(fetch, r, b, gbase, s, a6, d6);
+    }
+  } else {
+    double a1[40];
+    level1_exact(fetch, r, b, gbase, s, a1);
+    halo<32, true>(a1, nullptr, gbase, s);
+    dwt8_levels2to6<false, true>(a1, nullptr, gbase, s, a6, d6);
+  }
+}
+// The signal's X^2 for the guard's first stage (guard.h): MEASURED from the 8 lanes' tracked
+// ymax (float32 recordings; the tracking variants' second stage), else the a-priori int16 bound.
+template <bool MEASURED>
+__device__ __forceinline__ double signal_x2(float ymax, float r, float b) {
+  if constexpr (MEASURED) {
+    const double X = (double)group8_max(ymax);
+    return X * X;
+  } else {
+    return guard_x2_int16(r, b);
+  }
 }
 
 // A double moved across lanes by one DPP control (both halves), e.g. 0xB1 = xor 1, 0x4E = xor 2
@@ -728,6 +765,19 @@ __device__ __forceinline__ void dwt8_exact_row_wave(Sample sample, int C, int nf
     dwt8_exact_channel_wave([&](int k) { return sample(c, k); }, nfeat, scratch, row + c * nfeat,
                             lane);
   dwt8_normalise_row_wave(row, C * nfeat, scratch, lane);
+}
+
+// The same row by a workgroup of NW waves (every thread calls it): channels w, w + NW, ... by
+// wave w, each with its own 768 doubles of `scratch`, then a barrier and wave 0 normalises `row`
+// (16 features per channel).  The caller publishes the row with a barrier of its own.
+template <int NW, typename Sample>
+__device__ __forceinline__ void dwt8_exact_row_block(Sample sample, int C, double* scratch,
+                                                     double* row, int w, int lane) {
+#pragma unroll 1
+  for (int c = w; c < C; c += NW)
+    dwt8_exact_channel_wave([&](int k) { return sample(c, k); }, 16, scratch, row + c * 16, lane);
+  __syncthreads();
+  if (w == 0) dwt8_normalise_row_wave(row, 16 * C, scratch, lane);
 }
 
 // x[0..72): samples [64s, 64s+72) mod 512 of this lane's signal (level-0 slice + halo).

@@ -26,8 +26,8 @@
 //                   per-epoch LDS layout whose strides keep every half-wave of ds_read_u16 on
 //                   distinct banks; each lane folds the window's sub-16-byte misalignment into
 //                   its read base.  Lanes decode (float)raw*res - b two samples at a time just in
-//                   time and run the filter bank (fma numerics: levels 1-5 collapsed,
-//                   dwt8_collapsed_cascade; EXACT: value halos in the reference's order).  fma:
+//                   time and run the filter bank (dwt8.h signal_cascade -- fma numerics: levels
+//                   1-5 collapsed; EXACT: value halos in the reference's order).  fma:
 //                   every channel wave normalises and stores its 16 features of each row from
 //                   registers, the conditioning guard (guard.h) testing each row; EXACT: one wave
 //                   normalises the 8 x 48 features (sequential sum of squares,
@@ -217,37 +217,6 @@ __global__ __launch_bounds__((TILE * C + 63) / 64 * 64) void baseline_kernel(
 }
 
 
-// a3 + a6 + a7 fused into level 1 (dwt8.h level1_jit): (double)((float)raw * res - b), the
-// multiply and the subtraction each one correctly rounded fp32 operation
-// (DataProviderUtils.java:49-59, Baseline.java:39-41), two samples at a time with packed fp32
-// math, read straight from the staged window: own[k*CT] for k < 64, then the 8 halo samples
-// nxt[k*CT] of the next segment.
-// FMA numerics: dwt8_fast_cascade (own samples only; partial-sum halos); EXACT: level1_exact
-// (own samples; the 8 level-1 halo samples as decoded doubles from lane s+1) and value halos.
-template <int CT, bool FAST, bool TRACK = false>
-__device__ __forceinline__ void cascade_lds(const int16_t* own, const int16_t* nxt, float r,
-                                            float b, int gbase, int s, double& a6, double& d6,
-                                            float* ymax = nullptr) {
-  if constexpr (FAST) {
-#if EEGFX_COLLAPSED
-    if constexpr (TRACK) {
-      dwt8_collapsed_cascade<true>([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a6,
-                                   d6, ymax);
-    } else {
-      dwt8_collapsed_cascade([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a6, d6);
-    }
-#else
-    dwt8_fast_cascade([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a6, d6);
-#endif
-  } else {
-    double a1[40];
-    (void)nxt;
-    level1_exact([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a1);
-    halo<32, true>(a1, nullptr, gbase, s);
-    dwt8_levels2to6<FAST, true>(a1, nullptr, gbase, s, a6, d6);
-  }
-}
-
 // DMA rows of an epoch window: each row (one global_load_lds_dwordx4, lanes < SPR * SEGQ active)
 // carries SPR whole segments, so the lane's source offset is the same for every row:
 // lane l lands in segment SPR j + l / SEGQ, quad l % SEGQ, i.e. from byte
@@ -342,8 +311,9 @@ __device__ __forceinline__ void dma_fixup(const uint8_t* __restrict__ raw, int64
 // share the wave, L = 64, 32, 16 or 8 lanes per row for 1, 2, 3-4 or 5-8 rows; each lane
 // reads 512 / L consecutive frames of its row's window as staged in LDS (segment s at 16 SEGQ s
 // bytes past the epoch's misalignment) and keeps the column's min and max raw sample; those two
-// are decoded exactly as the kernel decodes every sample (x = fl(fl(raw * r) - b) is monotone in
-// raw), and X_c = max |x| is reduced over the row's lanes.  Returns X_c^2 on the lane sub == 0 of
+// are decoded exactly as the kernel decodes every sample (decode_f32, guard.h: monotone in raw),
+// and X_c = max |x| is reduced over the row's lanes (ladder_reduce).  Returns X_c^2 on the lane
+// sub == 0 of
 // each row's slot (0 elsewhere) and the epoch of the lane's slot in *row (-1 for lanes without
 // one).  delta, b: the misalignment and baseline of the lane's epoch (lane / 8), shuffled to the
 // slot's epoch.
@@ -388,19 +358,9 @@ __device__ __forceinline__ double channel_x2_rows(uint64_t flagged, const uint8_
     case 4: scan(std::integral_constant<int, 32>()); break;
     default: scan(std::integral_constant<int, 64>()); break;
   }
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  // (min, max) decoded as one pair: packed fp32 multiply and add, each lane rounded as the scalar
-  // fl(fl(raw * r) - b)
-  f32x2 x = f32x2{(float)mn, (float)mx} * f32x2{r, r};
-  x = x + f32x2{-be, -be};
-  // maximum over the row's L lanes (|x| >= 0: its bit pattern orders like the value)
-  uint32_t u = __float_as_uint(fmaxf(fabsf(x.x), fabsf(x.y)));
-  u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0xB1, 0xF, 0xF, true));
-  u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x4E, 0xF, 0xF, true));
-  u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x141, 0xF, 0xF, true));
-  if (sh >= 4) u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x140, 0xF, 0xF, true));
-  if (sh >= 5) u = max(u, (uint32_t)__shfl_xor((int)u, 16, 64));
-  if (sh >= 6) u = max(u, (uint32_t)__shfl_xor((int)u, 32, 64));
+  // maximum over the row's L lanes of |x| of the lane's extremes (decode_f32, guard.h)
+  const uint32_t u = ladder_reduce(__float_as_uint(decode_f32(mn, mx, r, be)), sh,
+                                   [](uint32_t a, uint32_t b) { return max(a, b); });
   const double X = (double)__uint_as_float(u);
   *row = valid && sub == 0 ? e : -1;
   return X * X;
@@ -465,8 +425,10 @@ __global__ __launch_bounds__(64 * C, 5) void window_kernel(
   float ymax = 0.0f;
   const uint8_t* eb = (const uint8_t*)(win + el * G::ESTR) + delta + 2 * col;
   const int16_t* own = (const int16_t*)(eb + 16 * G::SEGQ * s);
-  const int16_t* nxt = (const int16_t*)(eb + 16 * G::SEGQ * ((s + 1) & 7));
-  cascade_lds<CT, FAST, TRACKABLE>(own, nxt, r, b, lane & ~7, s, a6, d6, &ymax);
+  // a3 + a6 + a7 fused into the filter bank (dwt8.h signal_cascade), read straight from the
+  // staged window: own[k * CT], k < 64
+  signal_cascade<FAST, TRACKABLE>([&](int k) { return (float)own[k * CT]; }, r, b, lane & ~7, s,
+                                  a6, d6, &ymax);
 
   if constexpr (FAST) {
     // Each channel wave keeps its 16 features of each row in registers: the row's sum of squares
@@ -476,13 +438,9 @@ __global__ __launch_bounds__(64 * C, 5) void window_kernel(
     // then runs on all channel waves at once.
     const double q = group8_sum(__builtin_fma(a6, a6, d6 * d6));
     if constexpr (track) {
-      // the signal's measured X_c = max |x| over its 8 lanes (|x| >= 0 orders like its bits)
-      uint32_t u = __float_as_uint(ymax);
-      u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0xB1, 0xF, 0xF, true));
-      u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x4E, 0xF, 0xF, true));
-      u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x141, 0xF, 0xF, true));
-      const double X = (double)__uint_as_float(u);
-      if (s == 0) xs[el * C + w] = X * X;
+      // the signal's measured X_c^2, X_c = max |x| over its 8 lanes
+      const double x2 = signal_x2<true>(ymax, r, b);
+      if (s == 0) xs[el * C + w] = x2;
     }
     if (s == 0) part[el * C + w] = q;
     __syncthreads();
@@ -498,31 +456,21 @@ __global__ __launch_bounds__(64 * C, 5) void window_kernel(
     }
     const uint64_t flagged = __ballot(fails);  // bit 8e; the same mask in every channel wave
     uint64_t left = 0;
-    if (track && flagged) {  // the measured X_c of every row is already in LDS
+    if (flagged) {  // uniform over the workgroup, rare
+      if constexpr (!track) {  // scan: the flagged rows' measured X_c^2 go to LDS first (track:
+                               // every row's is there already)
+        int row;
+        const double x2 = channel_x2_rows<G::FB, G::SEGQ, G::ESTR * 4>(
+            flagged, (const uint8_t*)win, col, r, b, delta, lane, &row);
+        if (row >= 0) xs[row * C + w] = x2;
+        __syncthreads();
+      }
       bool f2 = false;
       if (s == 0 && ((flagged >> (8 * el)) & 1ull)) {
         double sx = xs[el * C];
 #pragma unroll
         for (int c = 1; c < C; ++c) sx += xs[el * C + c];
-        f2 = guard_fails(acc, kGuardK2Collapsed, sx * (1.0 + 0x1p-20));
-      }
-      left = __ballot(f2);
-      if (w == 0 && lane == 0) {
-        guard_count_rechecked(guard, __popcll(flagged));
-        if (left) guard_count_recomputed(guard, (unsigned long long)__popcll(left));
-      }
-    } else if (flagged) {  // uniform over the workgroup, rare
-      int row;
-      const double x2 = channel_x2_rows<G::FB, G::SEGQ, G::ESTR * 4>(
-          flagged, (const uint8_t*)win, col, r, b, delta, lane, &row);
-      if (row >= 0) xs[row * C + w] = x2;
-      __syncthreads();
-      bool f2 = false;
-      if (s == 0 && ((flagged >> (8 * el)) & 1ull)) {
-        double sx = xs[el * C];
-#pragma unroll
-        for (int c = 1; c < C; ++c) sx += xs[el * C + c];
-        f2 = guard_fails(acc, kGuardK2Collapsed, sx * (1.0 + 0x1p-20));
+        f2 = guard_fails_measured(acc, sx);
       }
       left = __ballot(f2);
       if (w == 0 && lane == 0) {
@@ -542,26 +490,16 @@ __global__ __launch_bounds__(64 * C, 5) void window_kernel(
       // them, the barrier above), then normalised and stored by wave 0
       double* scratch = (double*)win + w * 768;
       double* rowbuf = (double*)win + C * 768;
+      const Recording<int16_t> rec{raw, n_frames, CT};
       for (uint64_t f = left; f; f &= f - 1) {
         const int e = (__ffsll((unsigned long long)f) - 1) >> 3;
-        const int64_t B = wb[e0 + e] & ~(int64_t)1;  // byte offset of the window
-        const int64_t f0 = B / G::FB;
-        dwt8_exact_channel_wave(
-            [&](int k) {
-              const float bc = base[(e0 + e) * C + w];
-              const float v = f0 + k < n_frames
-                                  ? (float)*(const int16_t*)(raw + B + (int64_t)k * G::FB + 2 * col)
-                                  : 0.0f;
-              float y = v * r;
-              y = y - bc;
-              return (double)y;
-            },
-            16, scratch, rowbuf + w * 16, lane);
-        __syncthreads();
-        if (w == 0) {
-          dwt8_normalise_row_wave(rowbuf, F, scratch, lane);
+        const int64_t f0 = (wb[e0 + e] & ~(int64_t)1) / G::FB;  // first frame of the window
+        dwt8_exact_row_block<C>(
+            // C waves: the one channel wave w is asked for is its own, c = w
+            [&](int, int k) { return rec.x(f0 + k, col, r, base[(e0 + e) * C + w]); },
+            C, scratch, rowbuf, w, lane);
+        if (w == 0)
           for (int i = lane; i < F; i += 64) out[(e0 + e) * F + i] = rowbuf[i];
-        }
         __syncthreads();
       }
     }

@@ -26,11 +26,20 @@
 //   flat stretch decodes to ~1e-3 against X ~ 6e3), hence the second stage; for float32 recordings
 //   and caller-supplied double epochs the measured max |x| of the window from the start (no
 //   a-priori bound exists).
+//
+// The pieces of the verdict, one copy each, are here: the decode of a sample and of a pair of
+// extremes (decode_f32), the reduction ladder over a lane group (ladder_reduce: group_max_u32,
+// group_min_pk_i16), the two tests (guard_fails; guard_fails_measured, the only place the
+// measured sum's 2^-20 margin is applied: every helper that measures returns the bare sum), the
+// measured sum of a row by one wave (guard_measured_x2_wave), the whole verdict on a row by one
+// wave (guard_row_fails_wave) and the samples of a recording for the rare paths (Recording).
+// The kernels keep only how their lanes map to rows, channels and frames.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace eegfx {
 
@@ -165,22 +174,6 @@ __device__ __forceinline__ void guard_count_rechecked(const Guard& g, int rows) 
   if (g.rechecked && rows) guard_slot_add(g.rechecked, (unsigned long long)rows);
 }
 
-// Wave-wide minimum of packed int16 pairs (every lane gets it): the 16 lanes of a DPP row by
-// quad_perm xor 1 / xor 2, row_half_mirror and row_mirror (no LDS), then across the four rows.
-__device__ __forceinline__ uint32_t wave_pk_min_i16(uint32_t v) {
-  typedef short s2 __attribute__((ext_vector_type(2)));
-  auto mn = [](uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(s2, a),
-                                                                  __builtin_bit_cast(s2, b)));
-  };
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));
-  v = mn(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));
-  v = mn(v, (uint32_t)__shfl_xor((int)v, 16, 64));
-  return mn(v, (uint32_t)__shfl_xor((int)v, 32, 64));
-}
-
 // lane j's v (j wave-uniform), as a wave-uniform value
 __device__ __forceinline__ double lane_value(double v, int j) {
   const uint64_t b = __builtin_bit_cast(uint64_t, v);
@@ -189,14 +182,66 @@ __device__ __forceinline__ double lane_value(double v, int j) {
   return __builtin_bit_cast(double, (uint64_t)hi << 32 | lo);
 }
 
-// Wave-wide maximum of unsigned words (every lane gets it), the same moves as wave_pk_min_i16.
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__shfl_xor((int)v, 16, 64));
-  return max(v, (uint32_t)__shfl_xor((int)v, 32, 64));
+// The kernels' decode of a raw sample v (int16 or float32, as float) with resolution r and
+// baseline b: x = fl(fl(v * r) - b), two correctly rounded fp32 operations
+// (DataProviderUtils.java:49-59, Baseline.java:39-41; the file is compiled with
+// -ffp-contract=off).  Every sample the guard measures or recomputes goes through here.
+__device__ __forceinline__ float decode_f32(float v, float r, float b) {
+  float y = v * r;
+  y = y - b;
+  return y;
+}
+// The decode is monotone in v, so the extremes (lo, hi) of a set of raw samples bound its |x|:
+// max(|x(lo)|, |x(hi)|), the pair decoded with packed fp32 math (each half rounded as above).
+__device__ __forceinline__ float decode_f32(int lo, int hi, float r, float b) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  f32x2 x = f32x2{(float)lo, (float)hi} * f32x2{r, r};
+  x = x + f32x2{-b, -b};
+  return fmaxf(fabsf(x.x), fabsf(x.y));
+}
+
+// The reduction ladder over an aligned group of 2^lg lanes (lg = 3..6; every lane of the group
+// gets the result), the one copy of its steps: step i combines lanes 2^i apart -- quad_perm
+// xor 1 and xor 2, row_half_mirror and row_mirror as DPP moves (no LDS), then the two
+// cross-row shuffles.  lg may be a runtime value (channel_x2_rows); a constant folds the tests.
+template <int STEP>
+__device__ __forceinline__ uint32_t ladder_peer(uint32_t v) {
+  static_assert(STEP >= 0 && STEP < 6, "a wave has 64 lanes");
+  constexpr int kCtrl[4] = {0xB1, 0x4E, 0x141, 0x140};
+  if constexpr (STEP < 4)
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, kCtrl[STEP], 0xF, 0xF, true);
+  else
+    return (uint32_t)__shfl_xor((int)v, 1 << STEP, 64);
+}
+template <typename Op>
+__device__ __forceinline__ uint32_t ladder_reduce(uint32_t v, int lg, Op op) {
+  v = op(v, ladder_peer<0>(v));
+  v = op(v, ladder_peer<1>(v));
+  v = op(v, ladder_peer<2>(v));
+  if (lg >= 4) v = op(v, ladder_peer<3>(v));
+  if (lg >= 5) v = op(v, ladder_peer<4>(v));
+  if (lg >= 6) v = op(v, ladder_peer<5>(v));
+  return v;
+}
+constexpr int ladder_log2(int lanes) {
+  return lanes == 8 ? 3 : lanes == 16 ? 4 : lanes == 32 ? 5 : 6;
+}
+// Maximum of unsigned words over a group of LANES lanes.  A non-negative, non-NaN float orders
+// like its bit pattern, so this is also the maximum of such floats (max |x|).
+template <int LANES>
+__device__ __forceinline__ uint32_t group_max_u32(uint32_t v) {
+  static_assert(LANES == 8 || LANES == 16 || LANES == 32 || LANES == 64, "an aligned lane group");
+  return ladder_reduce(v, ladder_log2(LANES), [](uint32_t a, uint32_t b) { return max(a, b); });
+}
+// Minimum of packed int16 pairs over a group of LANES lanes.
+template <int LANES>
+__device__ __forceinline__ uint32_t group_min_pk_i16(uint32_t v) {
+  static_assert(LANES == 8 || LANES == 16 || LANES == 32 || LANES == 64, "an aligned lane group");
+  typedef short s2 __attribute__((ext_vector_type(2)));
+  return ladder_reduce(v, ladder_log2(LANES), [](uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(s2, a),
+                                                                  __builtin_bit_cast(s2, b)));
+  });
 }
 
 // Packs a lane's (min, max) of int16 samples as (min, ~max) so that one packed minimum reduces
@@ -207,21 +252,22 @@ __device__ __forceinline__ uint32_t guard_pack_minmax(int mn, int mx) {
 __device__ __forceinline__ int guard_unpack_min(uint32_t p) { return (int)(int16_t)(p & 0xFFFFu); }
 __device__ __forceinline__ int guard_unpack_max(uint32_t p) { return ~(int)(int16_t)(p >> 16); }
 
+// The second stage's test: `sum_x2` is a measured sum of X_c^2 (or a bound of it: 3 max_c X_c^2,
+// rows.h recheck_c3) as its helper returns it, bare; the 2^-20 margin that covers the rounding
+// of the decoded extremes' squares and of their sum is applied here and nowhere else.
+__device__ __forceinline__ bool guard_fails_measured(double acc, double sum_x2) {
+  return guard_fails(acc, kGuardK2Collapsed, sum_x2 * (1.0 + 0x1p-20));
+}
+
 // The second stage, by one wave (every lane calls it; the result is wave-uniform): sum over the
 // row's C signals of X_c^2, X_c = max_k |x_c[k]| over the 512 window samples, measured.
 // sample(c, k) returns the int16 raw value of sample k of channel c (0 for the zero padding past
-// the recording's end); the decode x = fl(fl(raw * r) - b) is monotone in raw, so X_c =
-// max(|x(min raw)|, |x(max raw)|) with decode(c, v) the kernels' own fp32 decode.  16 lanes (one
-// DPP row) per channel, four channels per pass; each lane's 32 reads are independent.  The
-// 2^-20 margin covers the rounding of the sum.
-template <typename Sample, typename Decode>
-__device__ __forceinline__ double guard_measured_x2_wave(Sample sample, Decode decode, int C,
+// the recording's end); X_c is decode_f32 of the channel's extremes with res(c) and base(c).
+// 16 lanes (one DPP row) per channel, four channels per pass; each lane's 32 reads are
+// independent.  Returns the bare sum (guard_fails_measured).
+template <typename Sample, typename Res, typename Base>
+__device__ __forceinline__ double guard_measured_x2_wave(Sample sample, Res res, Base base, int C,
                                                          int lane) {
-  typedef short s2 __attribute__((ext_vector_type(2)));
-  auto mn = [](uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(s2, a),
-                                                                  __builtin_bit_cast(s2, b)));
-  };
   const int grp = lane >> 4, l = lane & 15;
   double sx = 0.0;
 #pragma unroll 1
@@ -234,20 +280,67 @@ __device__ __forceinline__ double guard_measured_x2_wave(Sample sample, Decode d
       lo = min(lo, v);
       hi = max(hi, v);
     }
-    uint32_t p = guard_pack_minmax(lo, hi);  // reduced over the DPP row = this channel's lanes
-    p = mn(p, (uint32_t)__builtin_amdgcn_mov_dpp((int)p, 0xB1, 0xF, 0xF, true));
-    p = mn(p, (uint32_t)__builtin_amdgcn_mov_dpp((int)p, 0x4E, 0xF, 0xF, true));
-    p = mn(p, (uint32_t)__builtin_amdgcn_mov_dpp((int)p, 0x141, 0xF, 0xF, true));
-    p = mn(p, (uint32_t)__builtin_amdgcn_mov_dpp((int)p, 0x140, 0xF, 0xF, true));
-    const double X = fmax(fabs(decode(c, (float)guard_unpack_min(p))),
-                          fabs(decode(c, (float)guard_unpack_max(p))));
+    // reduced over the DPP row = this channel's lanes
+    const uint32_t p = group_min_pk_i16<16>(guard_pack_minmax(lo, hi));
+    const double X = (double)decode_f32(guard_unpack_min(p), guard_unpack_max(p), res(c), base(c));
     double x2 = c0 + grp < C ? X * X : 0.0;
     x2 += __shfl_xor(x2, 16, 64);
     x2 += __shfl_xor(x2, 32, 64);
     sx += x2;
   }
-  return sx * (1.0 + 0x1p-20);
+  return sx;
 }
+
+// The verdict on one row by one wave (every lane calls it; the result is wave-uniform), for the
+// kernels whose rows a single wave normalises (window_wide_kernel, the 32-channel kernel, the
+// staged one-pass writers).  acc, sx: this lane's shares of the row's sum of squares and of the
+// first stage's sum of X_c^2, summed over the wave here (acc returns the row's sum).  A row that
+// fails the first stage is counted in `rechecked` and tested again with stage2(), a
+// wave-collective call that returns the measured sum of X_c^2, bare: a scan
+// (guard_measured_x2_wave) or the tracked per-channel values (guard_tracked_x2_wave).
+// GuardMeasuredFirst instead: sx was the measured sum already (float32 recordings), the first
+// test is the only one.  `on`: the caller's own enable condition.
+struct GuardMeasuredFirst {};
+template <typename Stage2>
+__device__ __forceinline__ bool guard_row_fails_wave(double& acc, double sx, bool on,
+                                                     Stage2 stage2, const Guard& g, int lane) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    acc += __shfl_xor(acc, off, 64);
+    sx += __shfl_xor(sx, off, 64);
+  }
+  bool fails = on && guard_fails(acc, kGuardK2Collapsed, sx);
+  if (fails) {  // wave-uniform, rare
+    if (lane == 0) guard_count_rechecked(g, 1);
+    if constexpr (!std::is_same<Stage2, GuardMeasuredFirst>::value)
+      fails = guard_fails_measured(acc, stage2());
+  }
+  return fails;
+}
+// stage2 of guard_row_fails_wave from measured X_c^2 that the filter pass left in LDS (C <= 64).
+__device__ __forceinline__ double guard_tracked_x2_wave(const double* x2, int C, int lane) {
+  double sm = lane < C ? x2[lane] : 0.0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off, 64);
+  return sm;
+}
+
+// Samples of a multiplexed recording of T (int16_t or float) for the guard's rare paths, which
+// read the recording itself: frame f, column col, zero past the recording's end
+// (Arrays.copyOfRange's padding; toFloatArray -> 0.0f).  f >= 0 (a window follows its marker).
+template <typename T>
+struct Recording {
+  const uint8_t* raw;
+  int64_t n_frames;
+  int ct;
+  __device__ __forceinline__ float sample(int64_t f, int col) const {
+    return f < n_frames ? (float)*(const T*)(raw + (f * ct + col) * (int64_t)sizeof(T)) : 0.0f;
+  }
+  // the decoded sample, as every kernel decodes it
+  __device__ __forceinline__ double x(int64_t f, int col, float r, float b) const {
+    return (double)decode_f32(sample(f, col), r, b);
+  }
+};
 
 }  // namespace dev
 }  // namespace eegfx

@@ -36,30 +36,21 @@ namespace dev {
 // Window samples of (epoch e, channel c) from the multiplexed recording: frame pos + 175 + k.
 template <typename T>
 struct RawWindows {
-  const uint8_t* raw;
-  int64_t n_frames;
-  int ct;
+  Recording<T> rec;
   ChanSel sel;
   const int64_t* pos;
   const float* base;  // [n][C] baselines of the baseline kernel
   int C;
   // x[0..72) = samples [64 s, 64 s + 72) mod 512 of the window, decoded
   __device__ __forceinline__ void window(int64_t e, int c, int s, double (&x)[kIn]) const {
-    const int64_t p0 = pos[e];
+    const int64_t p0 = pos[e], n_frames = rec.n_frames;
     const int64_t p = p0 >= kPre && p0 - kPre <= n_frames ? p0 : (int64_t)kPre;  // as the kernels
     const float r = sel.res[c];
     const float b = base[e * C + c];
     const int col = sel.col[c];
 #pragma unroll
-    for (int k = 0; k < kIn; ++k) {
-      const int64_t f = p + 175 + ((kSegLen * s + k) & (kWin - 1));
-      // Arrays.copyOfRange zero-pads past the end of the recording (toFloatArray -> 0.0f)
-      const float v = f < n_frames ? (float)*(const T*)(raw + (f * ct + col) * (int64_t)sizeof(T))
-                                   : 0.0f;
-      float y = v * r;
-      y = y - b;
-      x[k] = (double)y;
-    }
+    for (int k = 0; k < kIn; ++k)
+      x[k] = rec.x(p + 175 + ((kSegLen * s + k) & (kWin - 1)), col, r, b);
   }
 };
 
@@ -107,13 +98,13 @@ hipError_t launch_guard_fixup_raw(hipStream_t st, const void* raw, int fmt, int6
                                   const void* scratch, const Guard& g, double* out) {
   if (!g.count) return hipSuccess;
   if (fmt == 0) {
-    dev::RawWindows<int16_t> src{(const uint8_t*)raw, n_frames, ct, sel, pos,
+    dev::RawWindows<int16_t> src{{(const uint8_t*)raw, n_frames, ct}, sel, pos,
                                  (const float*)scratch, C};
     hipLaunchKernelGGL(dev::exact_rows_kernel<dev::RawWindows<int16_t>>, dim3(kGuardGrid),
                        dim3(kGuardBlock), 0, st, src, 16, g, out);
   } else {
-    dev::RawWindows<float> src{(const uint8_t*)raw, n_frames, ct, sel, pos, (const float*)scratch,
-                               C};
+    dev::RawWindows<float> src{{(const uint8_t*)raw, n_frames, ct}, sel, pos,
+                               (const float*)scratch, C};
     hipLaunchKernelGGL(dev::exact_rows_kernel<dev::RawWindows<float>>, dim3(kGuardGrid),
                        dim3(kGuardBlock), 0, st, src, 16, g, out);
   }

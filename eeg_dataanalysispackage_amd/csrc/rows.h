@@ -1,6 +1,8 @@
 // rows.h -- normalisation and store of the feature rows of an 8-epoch sub-tile, shared by the
 // fused window kernel (fused.hip: its EXACT rows; its fma rows leave from registers) and the
-// one-pass getData + features kernels (cut.hip: both numerics).
+// one-pass getData + features kernels (cut.hip: both numerics), and the second stage of the
+// conditioning guard for the one-pass 3-channel kernel (recheck_c3; the guard's shared pieces are
+// in guard.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,7 +41,7 @@ struct NoRecheck {  // no second stage: every flagged row is recomputed
   __device__ uint64_t operator()(uint64_t flagged, double) const { return flagged; }
 };
 // The second stage one row at a time: x2(e), a wave-collective call, returns row e's measured
-// sum of X_c^2 (recheck_c3 or guard_measured_x2_wave).
+// sum of X_c^2, bare (recheck_c3).
 template <typename X2>
 struct PerRowRecheck {
   X2 x2;
@@ -49,7 +51,7 @@ struct PerRowRecheck {
       const int e1 = __ffsll((unsigned long long)f) - 1;
       const double acc_e = lane_value(acc, e1);  // e1 is wave-uniform
       // the verdict is wave-uniform: a scalar branch keeps `left` in SGPRs
-      if (__builtin_amdgcn_readfirstlane(guard_fails(acc_e, kGuardK2Collapsed, x2(e1 >> 3)) ? 1 : 0))
+      if (__builtin_amdgcn_readfirstlane(guard_fails_measured(acc_e, x2(e1 >> 3)) ? 1 : 0))
         left |= 1ull << e1;
     }
     return left;
@@ -129,50 +131,38 @@ __device__ __forceinline__ void normalise_store(double* fb, double* norm, double
   wave_sync();
 }
 
-// The conditioning guard's second stage (guard.h) for one row of the 3-channel kernels, by one
-// wave: lane l reads frames 64 (l >> 3) + 8 (l & 7) .. + 7 of the window, all three channels --
-// from the staged window `lds` (the window kernel's layout: segment s at 16 SEGQ s bytes past the
-// epoch's misalignment) or, when from_raw, from the recording (zero past its end, the reference's
-// padding) -- keeps each channel's min and max raw sample, decodes those six extremes exactly as
-// the kernel decodes every sample (x = fl(fl(raw * r) - b) is monotone in raw, so they bound the
-// lane's |x|), and takes one wave maximum: X = max_c max |x_c|.  It returns 3 X^2 >= sum_c X_c^2,
+// The conditioning guard's second stage (guard.h) for one row of the one-pass 3-channel kernel,
+// by one wave: lane l reads frames 64 (l >> 3) + 8 (l & 7) .. + 7 of the window at byte W of the
+// recording, all three channels (zero past its end, the reference's padding), keeps each
+// channel's min and max raw sample, decodes those six extremes exactly as the kernel decodes
+// every sample (decode_f32: monotone in raw, so they bound the lane's |x|), and takes one wave
+// maximum: X = max_c max |x_c|.  It returns 3 X^2 >= sum_c X_c^2, bare (guard_fails_measured),
 // a rigorous bound at most 3x looser than the per-channel sum (which would cost three wave
 // reductions: this pass is VALU-bound at the power cap, ~50 instead of ~100 VALU per row).
-// One LDS (or memory) round trip for all 24 samples of a lane.
-template <int FB, int SEGQ>
+// One memory round trip for all 24 samples of a lane.
+template <int FB>
 __device__ __forceinline__ double recheck_c3(const uint8_t* __restrict__ raw, int64_t n_frames,
                                              const ChanSel& sel, int64_t W,
-                                             const float* __restrict__ b, const uint8_t* lds,
-                                             bool from_raw, int lane) {
+                                             const float* __restrict__ b, int lane) {
   const int f0 = 8 * lane;  // = 64 (lane >> 3) + 8 (lane & 7)
   int v[3][8];
-  if (from_raw) {  // wave-uniform
-    const int64_t B = W & ~(int64_t)1;
-    const int64_t g0 = B / FB + f0;
-    if (B / FB + kWin <= n_frames) {  // wave-uniform: the whole window inside, no per-load test
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          v[c][i] = *(const int16_t*)(raw + B + (int64_t)(f0 + i) * FB + 2 * sel.col[c]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          v[c][i] = g0 + i < n_frames
-                        ? *(const int16_t*)(raw + B + (int64_t)(f0 + i) * FB + 2 * sel.col[c])
-                        : 0;
-    }
-  } else {
-    const uint8_t* p = lds + ((uint32_t)W & 14u) + 16 * SEGQ * (lane >> 3) +
-                       FB * 8 * (lane & 7);
+  const int64_t B = W & ~(int64_t)1;
+  const int64_t g0 = B / FB + f0;
+  if (B / FB + kWin <= n_frames) {  // wave-uniform: the whole window inside, no per-load test
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c][i] = *(const int16_t*)(p + FB * i + 2 * sel.col[c]);
+      for (int c = 0; c < 3; ++c)
+        v[c][i] = *(const int16_t*)(raw + B + (int64_t)(f0 + i) * FB + 2 * sel.col[c]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        v[c][i] = g0 + i < n_frames
+                      ? *(const int16_t*)(raw + B + (int64_t)(f0 + i) * FB + 2 * sel.col[c])
+                      : 0;
   }
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   float xm = 0.0f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -182,16 +172,10 @@ __device__ __forceinline__ double recheck_c3(const uint8_t* __restrict__ raw, in
       mn = min(mn, v[c][i]);
       mx = max(mx, v[c][i]);
     }
-    // (lo, hi) decoded as one pair: packed fp32 multiply and add, each lane rounded as the
-    // scalar fl(fl(raw * r) - b)
-    const float r = sel.res[c], bc = b[c];
-    f32x2 x = f32x2{(float)mn, (float)mx} * f32x2{r, r};
-    x = x + f32x2{-bc, -bc};
-    xm = fmaxf(xm, fmaxf(fabsf(x.x), fabsf(x.y)));
+    xm = fmaxf(xm, decode_f32(mn, mx, sel.res[c], b[c]));
   }
-  // |x| >= 0: its bit pattern orders like the value
-  const double X = (double)__uint_as_float(wave_max_u32(__float_as_uint(xm)));
-  return (X * X) * (3.0 * (1.0 + 0x1p-20));  // the constant is exact: 3 + 3 * 2^-20
+  const double X = (double)__uint_as_float(group_max_u32<64>(__float_as_uint(xm)));
+  return 3.0 * (X * X);  // exact: X^2 has 48 significant bits
 }
 
 }  // namespace dev

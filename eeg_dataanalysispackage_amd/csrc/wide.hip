@@ -216,29 +216,17 @@ __global__ __launch_bounds__(256) void window_wide_kernel(
     const int64_t B = (wpos(m) + 175) * FB;
     const uint8_t* eb = win + (size_t)m * EQ * 16 + (int)(B & 15) + sel.col[c] * (int)sizeof(T);
     const uint8_t* own = eb + 16 * SEGQ * s;
-    const uint8_t* nxt = eb + 16 * SEGQ * ((s + 1) & 7);
     const float r = sel.res[c];
     const float b = valid ? base[(e0 + m) * C + c] : 0.0f;
     double a6, d6;
-    if constexpr (FAST) {  // the 8 lanes of a group share the signal: partial-sum halos
-      constexpr bool MEASURE = !std::is_same<T, int16_t>::value;  // no a-priori bound for float32
-      float ym = 0.0f;
-      dwt8_collapsed_cascade<MEASURE>([&](int k) { return sample_at<T>(own + k * FB); }, r, b,
-                                      lane & ~7, s, a6, d6, &ym);
-      double x2;
-      if constexpr (MEASURE) {
-        const double X = (double)group8_max(ym);
-        x2 = X * X;
-      } else {
-        x2 = guard_x2_int16(r, b);
-      }
+    constexpr bool MEASURE = !std::is_same<T, int16_t>::value;  // no a-priori bound for float32
+    float ym = 0.0f;
+    // the 8 lanes of a group share the signal
+    signal_cascade<FAST, FAST && MEASURE>([&](int k) { return sample_at<T>(own + k * FB); }, r, b,
+                                          lane & ~7, s, a6, d6, &ym);
+    if constexpr (FAST) {
+      const double x2 = signal_x2<MEASURE>(ym, r, b);
       if (valid && s == 0) gx[m * C + c] = x2;
-    } else {
-      double a1[40];
-      (void)nxt;
-      level1_exact([&](int k) { return sample_at<T>(own + k * FB); }, r, b, lane & ~7, s, a1);
-      halo<32, true>(a1, nullptr, lane & ~7, s);
-      dwt8_levels2to6<FAST, true>(a1, nullptr, lane & ~7, s, a6, d6);
     }
     if (valid) {
       feat[m * F + c * 16 + s] = a6;
@@ -253,31 +241,26 @@ __global__ __launch_bounds__(256) void window_wide_kernel(
     for (int m = w; m < ne; m += blockDim.x / 64) {
       double acc = 0.0;
       for (int i = lane; i < F; i += 64) acc = __builtin_fma(feat[m * F + i], feat[m * F + i], acc);
-      double sx = lane < C ? gx[m * C + lane] : 0.0;  // C <= 64
-      for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_xor(acc, off, 64);
-        sx += __shfl_xor(sx, off, 64);
-      }
-      bool fails = guard.count && guard_fails(acc, kGuardK2Collapsed, sx);  // wave-uniform
-      if (std::is_same<T, int16_t>::value && fails) {  // the second stage on the staged window
-        if (lane == 0) guard_count_rechecked(guard, 1);
+      const double sx = lane < C ? gx[m * C + lane] : 0.0;  // C <= 64
+      bool fails;  // wave-uniform (guard.h guard_row_fails_wave)
+      if constexpr (std::is_same<T, int16_t>::value) {  // the second stage on the staged window
         const int64_t B = (wpos(m) + 175) * FB;
         const uint8_t* eb = win + (size_t)m * EQ * 16 + (int)(B & 15);
-        fails = guard_fails(
-            acc, kGuardK2Collapsed,
-            guard_measured_x2_wave(
-                [&](int c, int k) -> int {
-                  return (int)sample_at<T>(eb + sel.col[c] * (int)sizeof(T) + 16 * SEGQ * (k >> 6) +
-                                           FB * (k & 63));
-                },
-                [&](int c, float v) {
-                  float y = v * sel.res[c];
-                  y = y - base[(e0 + m) * C + c];
-                  return (double)y;
-                },
-                C, lane));
-      } else if (fails && lane == 0) {
-        guard_count_rechecked(guard, 1);  // float32: the first test is the measured one
+        fails = guard_row_fails_wave(
+            acc, sx, guard.count != nullptr,
+            [&] {
+              return guard_measured_x2_wave(
+                  [&](int c, int k) -> int {
+                    return (int)sample_at<T>(eb + sel.col[c] * (int)sizeof(T) +
+                                             16 * SEGQ * (k >> 6) + FB * (k & 63));
+                  },
+                  [&](int c) { return sel.res[c]; },
+                  [&](int c) { return base[(e0 + m) * C + c]; }, C, lane);
+            },
+            guard, lane);
+      } else {  // float32: the first test is the measured one
+        fails = guard_row_fails_wave(acc, sx, guard.count != nullptr, GuardMeasuredFirst{}, guard,
+                                     lane);
       }
       if (lane == 0) {
         norm[m] = rsqrt_nr(acc);  // the reciprocal norm (multiplied below)
@@ -394,32 +377,14 @@ __device__ __forceinline__ void c32_compute(const uint8_t* __restrict__ raw, int
   const int c = w * 8 + (lane >> 3), s = lane & 7;
   const uint8_t* eb = win + (int)(B & 15) + col_c * 2;
   const uint8_t* own = eb + 16 * SEGQ * s;
-  const uint8_t* nxt = eb + 16 * SEGQ * ((s + 1) & 7);
   double a6, d6;
   constexpr bool TRACK = FAST && TRK && EEGFX_GUARD;
-  if constexpr (FAST) {
-#if EEGFX_COLLAPSED
-    float ymax = 0.0f;
-    dwt8_collapsed_cascade<TRACK>([&](int k) { return sample_at<int16_t>(own + k * FB); }, r, b,
-                                  lane & ~7, s, a6, d6, &ymax);
-    if constexpr (TRACK) {  // the tracking variant: this channel's measured X_c over its 8 lanes
-      uint32_t u = __float_as_uint(ymax);
-      u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0xB1, 0xF, 0xF, true));
-      u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x4E, 0xF, 0xF, true));
-      u = max(u, (uint32_t)__builtin_amdgcn_mov_dpp((int)u, 0x141, 0xF, 0xF, true));
-      const double X = (double)__uint_as_float(u);
-      if (s == 0) sh.gxm[c] = X * X;
-    }
-#else
-    dwt8_fast_cascade([&](int k) { return sample_at<int16_t>(own + k * FB); }, r, b, lane & ~7, s,
-                      a6, d6);
-#endif
-  } else {
-    double a1[40];
-    (void)nxt;
-    level1_exact([&](int k) { return sample_at<int16_t>(own + k * FB); }, r, b, lane & ~7, s, a1);
-    halo<32, true>(a1, nullptr, lane & ~7, s);
-    dwt8_levels2to6<FAST, true>(a1, nullptr, lane & ~7, s, a6, d6);
+  float ymax = 0.0f;
+  signal_cascade<FAST, TRACK>([&](int k) { return sample_at<int16_t>(own + k * FB); }, r, b,
+                              lane & ~7, s, a6, d6, &ymax);
+  if constexpr (TRACK) {  // the tracking variant: this channel's measured X_c^2 over its 8 lanes
+    const double x2 = signal_x2<true>(ymax, r, b);
+    if (s == 0) sh.gxm[c] = x2;
   }
   double* feat = sh.feat;
   double* o = out + e * F;
@@ -432,35 +397,25 @@ __device__ __forceinline__ void c32_compute(const uint8_t* __restrict__ raw, int
       double acc = 0.0;
 #pragma unroll
       for (int k = 0; k < F / 64; ++k) acc = __builtin_fma(feat[lane + 64 * k], feat[lane + 64 * k], acc);
-      double sx = lane < C ? sh.gx[lane] : 0.0;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_xor(acc, off, 64);
-        sx += __shfl_xor(sx, off, 64);
-      }
-      bool fails = EEGFX_GUARD && guard.total && guard_fails(acc, kGuardK2Collapsed, sx);
-      if (TRACK && fails) {  // the second stage from the measured X_c of every channel
-        if (lane == 0) guard_count_rechecked(guard, 1);
-        double sm = lane < C ? sh.gxm[lane] : 0.0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off, 64);
-        fails = guard_fails(acc, kGuardK2Collapsed, sm * (1.0 + 0x1p-20));
-      } else if (fails) {  // wave-uniform, rare: the second stage on the staged window (intact)
-        if (lane == 0) guard_count_rechecked(guard, 1);
-        fails = guard_fails(
-            acc, kGuardK2Collapsed,
-            guard_measured_x2_wave(
-                [&](int cc, int k) -> int {
-                  return *(const int16_t*)(win + (int)(B & 15) + sel.col[cc] * 2 +
-                                           16 * SEGQ * (k >> 6) + FB * (k & 63));
-                },
-                [&](int cc, float v) {
-                  float y = v * sel.res[cc];
-                  y = y - base[e * C + cc];
-                  return (double)y;
-                },
-                C, lane));
-      }
+      const double sx = lane < C ? sh.gx[lane] : 0.0;
+      // wave-uniform (guard.h guard_row_fails_wave); the second stage from the measured X_c of
+      // every channel (TRACK) or on the staged window (intact)
+      const bool fails = guard_row_fails_wave(
+          acc, sx, EEGFX_GUARD && guard.total,
+          [&] {
+            if constexpr (TRACK) {
+              return guard_tracked_x2_wave(sh.gxm, C, lane);
+            } else {
+              return guard_measured_x2_wave(
+                  [&](int cc, int k) -> int {
+                    return *(const int16_t*)(win + (int)(B & 15) + sel.col[cc] * 2 +
+                                             16 * SEGQ * (k >> 6) + FB * (k & 63));
+                  },
+                  [&](int cc) { return sel.res[cc]; }, [&](int cc) { return base[e * C + cc]; },
+                  C, lane);
+            }
+          },
+          guard, lane);
       if (lane == 0) {
         sh.norm1 = rsqrt_nr(acc);
         sh.redo = fails;
@@ -473,29 +428,13 @@ __device__ __forceinline__ void c32_compute(const uint8_t* __restrict__ raw, int
       constexpr int NW = 256 / 64;
       static_assert(NW * 768 * 8 <= K::EQ * 16, "EXACT scratch fits the window buffer");
       const int64_t f0 = B / FB;
-      double* scratch = (double*)win + w * 768;
-#pragma unroll 1
-      for (int cc = w; cc < C; cc += NW) {
-        const int col = sel.col[cc];
-        const float rc = sel.res[cc], bc = base[e * C + cc];
-        dwt8_exact_channel_wave(
-            [&](int k) {
-              const float x = f0 + k < n_frames
-                                  ? (float)*(const int16_t*)(raw + B + (int64_t)k * FB + 2 * col)
-                                  : 0.0f;
-              float y = x * rc;
-              y = y - bc;
-              return (double)y;
-            },
-            16, scratch, feat + cc * 16, lane);
-      }
-      __syncthreads();
-      if (w == 0) {
-        dwt8_normalise_row_wave(feat, F, scratch, lane);
-        if (lane == 0) {
-          sh.norm1 = 1.0;  // the row is normalised
-          guard_count_recomputed(guard, 1ull);
-        }
+      const Recording<int16_t> rec{raw, n_frames, FB / 2};
+      dwt8_exact_row_block<NW>(
+          [&](int cc, int k) { return rec.x(f0 + k, sel.col[cc], sel.res[cc], base[e * C + cc]); },
+          C, (double*)win + w * 768, feat, w, lane);
+      if (w == 0 && lane == 0) {
+        sh.norm1 = 1.0;  // the row is normalised
+        guard_count_recomputed(guard, 1ull);
       }
       __syncthreads();
     }

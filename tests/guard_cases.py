@@ -87,14 +87,14 @@ def lanes_per_row(k):
 #       "epochs"   the same, with guard_acc_out_of_range                      (caller's epochs)
 Site = namedtuple("Site", "n kernel form where")
 SITES = {
-    1: Site(1, "window_kernel", "sum", "fused.hip channel_x2_rows (scan)"),
-    2: Site(2, "window_kernel", "sum", "fused.hip TRK: ymax, three-step DPP maximum"),
+    1: Site(1, "window_kernel", "sum", "fused.hip channel_x2_rows (scan), guard.h ladder_reduce"),
+    2: Site(2, "window_kernel", "sum", "fused.hip TRK: ymax, dwt8.h signal_x2 / group8_max"),
     3: Site(3, "cut_features_c3_kernel", "3max", "rows.h recheck_c3 from the recording"),
     4: Site(4, "window_wide_kernel", "sum", "guard.h guard_measured_x2_wave, int16"),
-    5: Site(5, "window_wide_kernel", "measured", "wide.hip group8_max(ym), float32"),
+    5: Site(5, "window_wide_kernel", "measured", "wide.hip signal_x2(ym), float32"),
     6: Site(6, "window_c32_kernel", "sum", "guard_measured_x2_wave at C = 32 (scan)"),
-    7: Site(7, "window_c32_kernel", "sum", "wide.hip TRACK: sh.gxm[]"),
-    8: Site(8, "cut_write_lds*_kernel", "sum", "cut.hip staged_features: gsmp / group8_max"),
+    7: Site(7, "window_c32_kernel", "sum", "wide.hip TRACK: sh.gxm[], guard_tracked_x2_wave"),
+    8: Site(8, "cut_write_lds*_kernel", "sum", "cut.hip staged_features: gsmp / signal_x2"),
     9: Site(9, "features_from_epochs_kernel", "epochs", "extract.hip group8_max(xm), sx"),
 }
 

@@ -19,6 +19,9 @@ FILES = ("fused.hip", "wide.hip", "dwt8.h")
 DMA_ISSUE = """  if (dma_issue<CT, C, NT>(raw, nbytes, wb, e0, ne, win, w, lane, rows))
     dma_fixup<CT, C>(raw, nbytes, wb, e0, ne, win, w, lane, rows);"""
 
+SIGNAL_CASCADE = """  signal_cascade<FAST, TRACKABLE>([&](int k) { return (float)own[k * CT]; }, r, b, lane & ~7, s,
+                                  a6, d6, &ymax);"""
+
 FMA_BODY = """#pragma unroll
   for (int q = 0; q < 3; ++q) {
     A0[q] = n == 0 ? x1 * R[q] : __builtin_fma(x1, R[q], A0[q]);
@@ -91,8 +94,8 @@ ABLATIONS = {
         "no window DMA, no LDS sample reads (wrong results)",
         [("fused.hip", DMA_ISSUE,
           "  (void)rows;  // ablation: no LDS staging; the lane's 64 samples come from VGPRs"),
-         ("fused.hip", """  cascade_lds<CT, FAST, TRACKABLE>(own, nxt, r, b, lane & ~7, s, a6, d6, &ymax);""",
-          """  (void)own; (void)nxt;
+         ("fused.hip", SIGNAL_CASCADE,
+          """  (void)own;
   u32x4_a4 q[8];
   {
     const int64_t wv = mine ? wb[e0 + el] : 0;
@@ -107,11 +110,11 @@ ABLATIONS = {
     "noldsread": (
         "no LDS sample reads: each sample is an opaque per-lane float plus its index (one fp32 "
         "add in place of the int16 conversion); window DMA, decode and fp64 kept (wrong results)",
-        [("fused.hip",
-          "      dwt8_collapsed_cascade([&](int k) { return (float)own[k * CT]; }, r, b, gbase, s, a6, d6);",
-          "      float q = (float)((int)(uintptr_t)own & 1023);  // ablation: no LDS sample reads\n"
-          "      asm volatile(\"\" : \"+v\"(q));\n"
-          "      dwt8_collapsed_cascade([&](int k) { return q + (float)k; }, r, b, gbase, s, a6, d6);")]),
+        [("fused.hip", SIGNAL_CASCADE,
+          "  float q = (float)((int)(uintptr_t)own & 1023);  // ablation: no LDS sample reads\n"
+          "  asm volatile(\"\" : \"+v\"(q));\n"
+          "  signal_cascade<FAST, TRACKABLE>([&](int k) { return q + (float)k; }, r, b, lane & ~7, s,\n"
+          "                                  a6, d6, &ymax);")]),
     "nofp64": (
         "fp64 filter bank removed: the 440 multiply-adds and adds per lane become 64 fp64 adds; "
         "DMA, LDS reads and decode kept (wrong results)",
