@@ -12,7 +12,8 @@ Host mirror of the reference's hot-path API over the libeegfx C ABI (include/eeg
   :func:`nn_train`, :func:`nn_train_opt`, :func:`nn_predict`, :func:`nn_statistics` --
   train_clf=nn
   (the other classifiers live in :mod:`classification`; :func:`pipeline.run_train_clf` is the
-  train/test flow over ``OffLineDataProvider.split`` with the rows resident on the device)
+  train/test flow over ``OffLineDataProvider.split`` with the rows resident on the device, and
+  with ``sharded=True`` over ``splitShards`` with every row left on its shard's context)
 * :mod:`brainvision` -- native .vhdr/.vmrk reader and marker planner
 """
 from ._lib import EegfxError, LIB_PATH, lib

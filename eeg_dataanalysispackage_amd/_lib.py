@@ -69,6 +69,18 @@ class OdpShard(Structure):
                 ("features_numerics", c_int32)]
 
 
+class SplitShard(Structure):
+    _fields_ = [("ctx_index", c_int32), ("pad", c_int32), ("n_train", c_int64),
+                ("n_test", c_int64), ("X_train", c_void_p), ("y_train", c_void_p),
+                ("pos_train", c_void_p), ("X_test", c_void_p), ("y_test", c_void_p),
+                ("pos_test", c_void_p)]
+
+
+class GlmShard(Structure):
+    _fields_ = [("ctx", c_void_p), ("X", c_void_p), ("y", c_void_p), ("pos", c_void_p),
+                ("n", c_int64)]
+
+
 ODP_MAX_SHARDS = 64
 GINI, ENTROPY = 0, 1
 SUBSET_AUTO, SUBSET_ALL, SUBSET_SQRT, SUBSET_LOG2, SUBSET_ONETHIRD = 0, 1, 2, 3, 4
@@ -226,6 +238,17 @@ SIGNATURES = {
     "eegfx_confusion_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int]),
     "eegfx_odp_split": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int32, c_int32, c_int32,
                                 c_int32, c_void_p, c_void_p, POINTER(c_int64), c_int]),
+    "eegfx_split_shard_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_double, c_void_p,
+                                       c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "eegfx_odp_split_sharded": (c_int, [c_void_p, c_int64, c_double, c_int32, c_int32, c_int32,
+                                        c_int32, POINTER(SplitShard)]),
+    "eegfx_glm_sgd_train_sharded": (c_int, [c_int, POINTER(GlmShard), c_int32, c_int32, c_int32,
+                                            c_double, c_double, c_double, c_double, c_int32,
+                                            c_void_p, POINTER(c_int32)]),
+    "eegfx_available_processors": (c_int, []),
+    "eegfx_glm_shard_state": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "eegfx_glm_count_sharded": (c_int, [c_int, POINTER(GlmShard), c_int32, c_int32, c_void_p,
+                                        c_double, c_double, c_void_p]),
     "eegfx_nn_param_count": (c_int64, [c_int32, POINTER(NnConfig)]),
     "eegfx_nn_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(NnConfig),
                                c_void_p, c_void_p, c_void_p, c_int]),

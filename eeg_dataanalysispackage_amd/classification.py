@@ -17,6 +17,10 @@ count actual-1 / predicted-0).  ``SVMClassifier`` is the same flow with MLlib 1.
 its ``config_layer<i>_*`` keys, as DESIGN.md section 10.7 defines it (``eegfx_nn_train`` /
 ``eegfx_nn_predict`` / ``eegfx_nn_statistics``); its statistics follow
 ``ClassificationStatistics.add``, not Spark's confusion matrix.
+``sgd_train_sharded`` / ``svm_sgd_train_sharded`` / ``count_sharded`` (and the classifiers'
+``trainShards`` / ``testShards``) are the two SGD classifiers over rows that stay on the contexts of
+a sharded provider (``eegfx_glm_sgd_train_sharded`` / ``eegfx_glm_count_sharded``, DESIGN.md section
+10.11).
 Model save/load (Spark model directories) is out of scope.
 """
 from __future__ import annotations
@@ -143,6 +147,123 @@ def svm_predict(ctx: Context, X, weights, intercept: float = 0.0,
     """SVMModel.predict on the device: margin w.x + b > threshold (0.0) -> 1 else 0, or the
     margin when ``threshold`` is None (clearThreshold)."""
     return _predict("eegfx_svm_predict", ctx, X, weights, intercept, threshold)
+
+
+# ---- the SGD classifiers over rows that stay on several contexts (DESIGN.md section 10.11) ------
+
+def _glm_shards(shards, with_pos=True):
+    """``shards``: (context, X, y[, pos]) per shard -- device tensors on the context's device, X
+    [n][d] float64, y [n] float64, pos [n] int64 or None.  Returns the eegfx_glm_shard array, what
+    keeps its tensors alive, d, and the (context, tensor) pairs to order the streams by."""
+    import torch
+    arr = (_lib.GlmShard * max(1, len(shards)))()
+    keep, order, d = [], [], None
+    for i, sh in enumerate(shards):
+        ctx, X, y = sh[0], sh[1], sh[2]
+        pos = sh[3] if len(sh) > 3 and with_pos else None
+        if not (_is_device(X) and _is_device(y)) or (pos is not None and not _is_device(pos)):
+            raise ValueError("the rows of a shard are device tensors")
+        X, y = _contig(X, np.float64), _contig(y, np.float64)
+        if X.ndim != 2 or y.ndim != 1 or int(y.shape[0]) != int(X.shape[0]):
+            raise ValueError(f"X must be [n][d] and y [n], got {tuple(X.shape)} and "
+                             f"{tuple(y.shape)}")
+        if d is None:
+            d = int(X.shape[1])
+        if int(X.shape[1]) != d:
+            raise ValueError(f"shard {i} has {int(X.shape[1])} features, shard 0 has {d}")
+        n = int(X.shape[0])
+        if pos is not None:
+            pos = pos.contiguous()
+            if pos.dtype != torch.int64 or tuple(pos.shape) != (n,):
+                raise ValueError(f"pos must be int64 [{n}]")
+        keep.append((X, y, pos))
+        arr[i] = _lib.GlmShard(ctx.handle, ptr(X) if n else None, ptr(y) if n else None,
+                               ptr(pos) if n and pos is not None else None, n)
+        if n:
+            order.append((ctx, X))
+    return arr, keep, d, order
+
+
+def _call_sharded(order, fn, *args):
+    """Context._call over several contexts: every context's stream is ordered after the torch
+    work that produced its shard's tensors, and torch's streams after the call."""
+    pairs = [ctx._enter_device(ref) for ctx, ref in order]
+    try:
+        _lib.check(fn(*args))
+    finally:
+        for (ctx, _), pair in zip(order, pairs):
+            ctx._leave_device(pair)
+
+
+def _train_sharded(grad, shards, num_iterations, step_size, reg_param, mini_batch_fraction,
+                   convergence_tol, initial_weights, num_partitions):
+    arr, keep, d, order = _glm_shards(shards)
+    if d is None:
+        raise ValueError("no shards")
+    w = (np.zeros(d) if initial_weights is None
+         else np.array(initial_weights, dtype=np.float64).copy())
+    if w.shape != (d,):
+        raise ValueError(f"initial_weights must be [{d}]")
+    it = c_int32()
+    parts = 1 if num_partitions is None else int(num_partitions)
+    _call_sharded(order, lib().eegfx_glm_sgd_train_sharded, grad, arr, len(shards), d,
+                  int(num_iterations), float(step_size), float(reg_param),
+                  float(mini_batch_fraction), float(convergence_tol), parts, ptr(w), byref(it))
+    return w, it.value
+
+
+def sgd_train_sharded(shards, num_iterations: int = DEFAULT_NUM_ITERATIONS,
+                      step_size: float = DEFAULT_STEP_SIZE, reg_param: float = 0.0,
+                      mini_batch_fraction: float = DEFAULT_MINI_BATCH_FRACTION,
+                      convergence_tol: float = CONVERGENCE_TOL, initial_weights=None,
+                      num_partitions: Optional[int] = None):
+    """sgd_train over rows that stay where they are (eegfx_glm_sgd_train_sharded).  ``shards``:
+    (context, X, y[, pos]) per shard, each context once; pos names the position of every row in
+    the whole training list (None: the shards' rows in shard order), which mini_batch_fraction < 1
+    samples as sgd_train does (num_partitions None: the processors available to the process).
+    Returns (weights, iterations_run); one shard gives sgd_train's bits."""
+    if num_partitions is None and mini_batch_fraction < 1.0:
+        num_partitions = int(lib().eegfx_available_processors())
+    return _train_sharded(0, shards, num_iterations, step_size, reg_param, mini_batch_fraction,
+                          convergence_tol, initial_weights, num_partitions)
+
+
+def svm_sgd_train_sharded(shards, num_iterations: int = DEFAULT_NUM_ITERATIONS,
+                          step_size: float = DEFAULT_STEP_SIZE,
+                          reg_param: float = DEFAULT_REG_PARAM,
+                          mini_batch_fraction: float = DEFAULT_MINI_BATCH_FRACTION,
+                          convergence_tol: float = CONVERGENCE_TOL, initial_weights=None):
+    """svm_sgd_train (full batch) over rows that stay where they are; see sgd_train_sharded."""
+    return _train_sharded(1, shards, num_iterations, step_size, reg_param, mini_batch_fraction,
+                          convergence_tol, initial_weights, None)
+
+
+def shard_state(ctx: Context, d: int):
+    """(iterations, flag, updates, weights) of the training state the last sharded run left on
+    ``ctx`` (eegfx_glm_shard_state): on every shard that took part, the root's bits."""
+    head = np.zeros(4, dtype=np.int32)
+    w = np.empty(d, dtype=np.float64)
+    _lib.check(lib().eegfx_glm_shard_state(ctx.handle, int(d), ptr(head), ptr(w)))
+    return int(head[0]), int(head[1]), int(head[2]), w
+
+
+def count_sharded(shards, weights, intercept: float = 0.0, threshold: Optional[float] = 0.5,
+                  svm: bool = False):
+    """(tp, tn, fp, fn) of the model's predictions over every shard's rows, scored and counted in
+    one kernel where the rows are (eegfx_glm_count_sharded): what predict / svm_predict followed
+    by confusion_counts gives on the rows together.  ``shards``: (context, X, y) per shard.
+    Raises as confusion_counts does."""
+    arr, keep, d, order = _glm_shards(shards, with_pos=False)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if d is None:
+        d = int(w.shape[0])
+    if w.shape != (d,):
+        raise ValueError(f"weights must be [{d}]")
+    counts = np.zeros(4, dtype=np.int64)
+    t = math.nan if threshold is None else float(threshold)
+    _call_sharded(order, lib().eegfx_glm_count_sharded, 1 if svm else 0, arr, len(shards), d,
+                  ptr(w), float(intercept), t, ptr(counts))
+    return tuple(int(v) for v in counts)
 
 
 # Strategy.defaultStrategy("Classification") (MLlib 1.6.2)
@@ -439,21 +560,42 @@ class LogisticRegressionClassifier(_Classifier):
         OffLineDataProvider.split returns them).  :85-114 -- the config_* keys select the static
         train(...) (regParam 0.0), otherwise the default LogisticRegressionWithSGD().run
         (regParam 0.01)."""
-        c = self.config
-        if all(k in c for k in ("config_num_iterations", "config_step_size",
-                                "config_mini_batch_fraction")):
-            self.weights, self.iterations_run = sgd_train(
-                self.context, X, y, num_iterations=int(c["config_num_iterations"]),
-                step_size=float(c["config_step_size"]), reg_param=0.0,
-                mini_batch_fraction=float(c["config_mini_batch_fraction"]),
-                num_partitions=self.num_partitions)
-        else:
-            self.weights, self.iterations_run = sgd_train(
-                self.context, X, y, DEFAULT_NUM_ITERATIONS, DEFAULT_STEP_SIZE, DEFAULT_REG_PARAM,
-                DEFAULT_MINI_BATCH_FRACTION)
+        self.weights, self.iterations_run = sgd_train(self.context, X, y, **self._sgd_config())
 
     def _predict_rows(self, features):
         return predict(self.context, features, self.weights)
+
+    # The flow over the provider's shards (OffLineDataProvider.splitShards): what trainFeatures /
+    # testFeatures do on the rows together, with the rows left on their contexts.
+    _SVM = False
+
+    def _sgd_config(self):
+        """trainFeatures' reading of the config as sgd_train's arguments."""
+        c = self.config
+        if all(k in c for k in ("config_num_iterations", "config_step_size",
+                                "config_mini_batch_fraction")):
+            return dict(num_iterations=int(c["config_num_iterations"]),
+                        step_size=float(c["config_step_size"]), reg_param=0.0,
+                        mini_batch_fraction=float(c["config_mini_batch_fraction"]),
+                        num_partitions=self.num_partitions)
+        return dict(num_iterations=DEFAULT_NUM_ITERATIONS, step_size=DEFAULT_STEP_SIZE,
+                    reg_param=DEFAULT_REG_PARAM, mini_batch_fraction=DEFAULT_MINI_BATCH_FRACTION)
+
+    def trainShards(self, split) -> None:
+        """trainFeatures on the training part of OffLineDataProvider.splitShards(), each shard's
+        rows on its own context (sgd_train_sharded)."""
+        shards = [(s.context, s.X_train, s.y_train, s.pos_train) for s in split]
+        fn = svm_sgd_train_sharded if self._SVM else sgd_train_sharded
+        self.weights, self.iterations_run = fn(shards, **self._sgd_config())
+
+    def testShards(self, split) -> ClassificationStatistics:
+        """testFeatures on the test part of splitShards(): scored and counted where the rows
+        are (count_sharded); the four integers of every shard come back."""
+        if not self._trained():
+            raise RuntimeError("The classifier has not been trained")
+        shards = [(s.context, s.X_test, s.y_test) for s in split]
+        return ClassificationStatistics(*count_sharded(
+            shards, self.weights, threshold=0.0 if self._SVM else 0.5, svm=self._SVM))
 
 
 class SVMClassifier(LogisticRegressionClassifier):
@@ -465,20 +607,24 @@ class SVMClassifier(LogisticRegressionClassifier):
         config_mini_batch_fraction all set, the static SVMWithSGD.train(rdd, iterations, step,
         regParam, fraction); otherwise new SVMWithSGD().run (step 1.0, 100 iterations,
         regParam 0.01, fraction 1.0)."""
-        c = self.config
-        if all(k in c for k in ("config_num_iterations", "config_step_size", "config_reg_param",
-                                "config_mini_batch_fraction")):
-            self.weights, self.iterations_run = svm_sgd_train(
-                self.context, X, y, num_iterations=int(c["config_num_iterations"]),
-                step_size=float(c["config_step_size"]), reg_param=float(c["config_reg_param"]),
-                mini_batch_fraction=float(c["config_mini_batch_fraction"]))
-        else:
-            self.weights, self.iterations_run = svm_sgd_train(
-                self.context, X, y, DEFAULT_NUM_ITERATIONS, DEFAULT_STEP_SIZE, DEFAULT_REG_PARAM,
-                DEFAULT_MINI_BATCH_FRACTION)
+        self.weights, self.iterations_run = svm_sgd_train(self.context, X, y,
+                                                          **self._sgd_config())
 
     def _predict_rows(self, features):
         return svm_predict(self.context, features, self.weights)
+
+    _SVM = True
+
+    def _sgd_config(self):
+        c = self.config
+        if all(k in c for k in ("config_num_iterations", "config_step_size", "config_reg_param",
+                                "config_mini_batch_fraction")):
+            return dict(num_iterations=int(c["config_num_iterations"]),
+                        step_size=float(c["config_step_size"]),
+                        reg_param=float(c["config_reg_param"]),
+                        mini_batch_fraction=float(c["config_mini_batch_fraction"]))
+        return dict(num_iterations=DEFAULT_NUM_ITERATIONS, step_size=DEFAULT_STEP_SIZE,
+                    reg_param=DEFAULT_REG_PARAM, mini_batch_fraction=DEFAULT_MINI_BATCH_FRACTION)
 
 
 def _tree_config(c: Dict[str, str]) -> dict:

@@ -43,6 +43,44 @@ int eegfx::available_processors() {
   return n;
 }
 
+bool eegfx::check_sgd_args(int grad, int32_t d, int32_t num_iterations, double mini_batch_fraction,
+                           int32_t num_partitions) {
+  check_train_d(d);
+  if (num_iterations < 0) fail(EEGFX_EINVAL, "num_iterations %d", num_iterations);
+  // RDD.sample's require(fraction >= 0.0), then BernoulliSampler's upper bound 1 up to
+  // RandomSampler.roundingEpsilon
+  if (!(mini_batch_fraction >= 0.0))
+    fail(EEGFX_EINVAL, "Negative fraction value: %g", mini_batch_fraction);
+  if (!(mini_batch_fraction <= 1.0 + 1e-6))
+    fail(EEGFX_EINVAL, "Sampling fraction (%g) must be on interval [0, 1]", mini_batch_fraction);
+  const bool sampled = mini_batch_fraction < 1.0;
+  if (sampled && grad != kGradLogistic)
+    fail(EEGFX_ENOTSUP, "miniBatchFraction %g: the SVM loop is full-batch only",
+         mini_batch_fraction);
+  if (sampled && num_partitions < 1) fail(EEGFX_EINVAL, "num_partitions %d", num_partitions);
+  return sampled;
+}
+
+// the masks of up to ~256 MB of iterations at a time
+int eegfx::sgd_mask_chunk(int64_t n, int num_iterations) {
+  const int64_t words = (n + 31) / 32;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(num_iterations, ((int64_t)64 << 20) / words));
+}
+
+// drawn by threads over iterations
+void eegfx::draw_sgd_masks(int64_t n, double fraction, int num_partitions, int i0, int k,
+                           uint32_t* masks, int64_t* counts) {
+  const int64_t words = (n + 31) / 32;
+  const int T = std::max(1, std::min({k, 64, available_processors()}));
+  Joiner pool;
+  for (int t = 0; t < T; ++t)
+    pool.th.emplace_back([=] {
+      for (int j = t; j < k; j += T)  // GradientDescent's i = i0 + j + 1, seed 42 + i
+        counts[j] = spark::sample_mask(n, fraction, num_partitions, 42 + (int64_t)(i0 + j + 1),
+                                       &masks[(size_t)j * words]);
+    });
+}
+
 // the classifier of LogisticRegressionClassifier.java:85-114 on the GPU
 // (csrc/logreg.hip): MLlib 1.6.2 LogisticRegressionWithSGD.  miniBatchFraction < 1: iteration i
 // trains on data.sample(false, f, 42 + i) of the rows in `num_partitions` ParallelCollectionRDD
@@ -59,19 +97,8 @@ static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double
     check_mem(mem);
     if (n < 1) fail(EEGFX_EINVAL, "empty training set");  // GeneralizedLinearAlgorithm: first()
     if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
-    check_train_d(d);
-    if (num_iterations < 0) fail(EEGFX_EINVAL, "num_iterations %d", num_iterations);
-    // RDD.sample's require(fraction >= 0.0), then BernoulliSampler's upper bound 1 up to
-    // RandomSampler.roundingEpsilon
-    if (!(mini_batch_fraction >= 0.0))
-      fail(EEGFX_EINVAL, "Negative fraction value: %g", mini_batch_fraction);
-    if (!(mini_batch_fraction <= 1.0 + 1e-6))
-      fail(EEGFX_EINVAL, "Sampling fraction (%g) must be on interval [0, 1]", mini_batch_fraction);
-    const bool sampled = mini_batch_fraction < 1.0;
-    if (sampled && grad != kGradLogistic)
-      fail(EEGFX_ENOTSUP, "miniBatchFraction %g: the SVM loop is full-batch only",
-           mini_batch_fraction);
-    if (sampled && num_partitions < 1) fail(EEGFX_EINVAL, "num_partitions %d", num_partitions);
+    const bool sampled =
+        check_sgd_args(grad, d, num_iterations, mini_batch_fraction, num_partitions);
     ctx->activate();
     const auto [dX, dy] = stage_xy(ctx, X, y, n, d, mem);
     const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
@@ -89,14 +116,11 @@ static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double
         HIP_CHECK(launch_lr_iteration(ctx->stream, grad, dX, dy, n, d, nullptr, n, st, part, G,
                                       step_size, reg_param, convergence_tol, num_iterations));
     } else {
-      // the masks of up to ~256 MB of iterations at a time, drawn by threads over iterations
       const int64_t words = (n + 31) / 32;
-      const int chunk = (int)std::max<int64_t>(
-          1, std::min<int64_t>(num_iterations, ((int64_t)64 << 20) / words));
+      const int chunk = sgd_mask_chunk(n, num_iterations);
       std::vector<uint32_t> masks((size_t)(chunk * words));
       std::vector<int64_t> counts((size_t)chunk);
       uint32_t* dmask = (uint32_t*)ctx->lr_mask.get(sizeof(uint32_t) * masks.size());
-      const int T_max = std::min(64, available_processors());
       for (int i0 = 0; i0 < num_iterations; i0 += chunk) {
         const int k = std::min(chunk, num_iterations - i0);
         ctx->drain();  // the previous chunk's upload and iterations are done with both buffers
@@ -107,17 +131,7 @@ static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double
           HIP_CHECK(hipStreamSynchronize(ctx->stream));
           if (conv != 0) break;
         }
-        const int T = std::max(1, std::min(k, T_max));
-        {
-          Joiner pool;
-          for (int t = 0; t < T; ++t)
-            pool.th.emplace_back([&, t] {
-              for (int j = t; j < k; j += T)  // GradientDescent's i = i0 + j + 1, seed 42 + i
-                counts[j] = spark::sample_mask(n, mini_batch_fraction, num_partitions,
-                                               42 + (int64_t)(i0 + j + 1),
-                                               &masks[(size_t)j * words]);
-            });
-        }
+        draw_sgd_masks(n, mini_batch_fraction, num_partitions, i0, k, masks.data(), counts.data());
         HIP_CHECK(hipMemcpyAsync(dmask, masks.data(), sizeof(uint32_t) * (size_t)(k * words),
                                  hipMemcpyHostToDevice, ctx->stream));
         for (int j = 0; j < k; ++j)
@@ -178,6 +192,8 @@ int eegfx_logreg_sgd_train(eegfx_ctx* ctx, const double* X, const double* y, int
                        mini_batch_fraction, convergence_tol, (int32_t)available_processors(),
                        weights, iterations_run, mem);
 }
+
+int eegfx_available_processors(void) { return available_processors(); }
 
 int eegfx_spark_sample(int64_t n, double fraction, int32_t num_partitions, int64_t seed,
                        uint32_t* mask, int64_t* kept) {

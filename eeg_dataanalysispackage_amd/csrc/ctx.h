@@ -1,8 +1,8 @@
 // ctx.h -- the device context (struct eegfx_ctx) and the helpers that the host sources share:
 // the staging of host-memory arguments (stage_in, dev_out, copy_out and what is built on them),
 // the argument checks (defined in api.cpp) and the device-pointer pipelines (routes.cpp), used by
-// api.cpp, routes.cpp, streamed.cpp, classify.cpp, nn.cpp, tree_driver.cpp, mailbox.cpp, flow.cpp
-// and odp.cpp (the OffLineDataProvider).
+// api.cpp, routes.cpp, streamed.cpp, classify.cpp, sharded.cpp, nn.cpp, tree_driver.cpp,
+// mailbox.cpp, flow.cpp and odp.cpp (the OffLineDataProvider).
 // Internal: not installed.
 #pragma once
 
@@ -182,6 +182,9 @@ struct eegfx_ctx {
   // eegfx_logreg_* / eegfx_svm_*: LrState (train: state and weights; predict: the weights), the
   // gradient partials, a chunk of mini-batch masks
   DevBuf lr_state, lr_part, lr_mask;
+  // eegfx_glm_sgd_train_sharded: the root's [shards][d] slots / another shard's folded d-vector;
+  // the positions of a shard given without them
+  DevBuf lr_fold, lr_pos;
   // eegfx_dtree_train / eegfx_rforest_train (dt_bin_rows, grow_trees): threshold table, bins, slot
   // + label per row, one group's histograms (and the gathered split sample).  dt_nodes: records
   // per node from the host -- a group's DtDecisions (train), the model's DtNodes
@@ -230,7 +233,8 @@ struct eegfx_ctx {
   // every DevBuf of the context: bound to the stream at creation, released at destruction
   auto buffers() {
     return std::array{&raw, &pos, &out, &scratch, &fused, &rows_x, &row_vals, &lr_state, &lr_part,
-                      &lr_mask, &guard_list, &dt_tab, &dt_bins, &dt_rows, &dt_hist, &dt_nodes,
+                      &lr_mask, &lr_fold, &lr_pos, &guard_list, &dt_tab, &dt_bins, &dt_rows,
+                      &dt_hist, &dt_nodes,
                       &rf_weight, &rf_slot, &rf_tab, &fl_src, &fl_idx, &fl_dst, &fl_lab, &fl_y,
                       &fl_flag, &nn_state, &nn_part, &nn_scores, &nn_in, &nn_stat,
                       &nn_opt, &nn_search};
@@ -420,6 +424,27 @@ void predict_frame(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d, double
 
 // The processors this process may run on (classify.cpp): Spark local[*]'s defaultParallelism.
 int available_processors();
+// classify.cpp, shared by the one-context trainer and the one over shards (sharded.cpp): the
+// argument ladder past the null and row-count checks (returns whether the run is sampled); the
+// iterations whose masks are drawn and uploaded at a time; and the masks of iterations i0 + 1 ..
+// i0 + k over n rows ((n + 31) / 32 words each) with their row counts, drawn by threads.
+bool check_sgd_args(int grad, int32_t d, int32_t num_iterations, double mini_batch_fraction,
+                    int32_t num_partitions);
+int sgd_mask_chunk(int64_t n, int num_iterations);
+void draw_sgd_masks(int64_t n, double fraction, int num_partitions, int i0, int k, uint32_t* masks,
+                    int64_t* counts);
+// `bytes` from src on context `from` to dst on context `to`, on `st`: a device-to-device copy
+// where the two share a device, a peer copy otherwise.
+inline void copy_between(void* dst, const eegfx_ctx* to, const void* src, const eegfx_ctx* from,
+                         size_t bytes, hipStream_t st) {
+  if (to->device == from->device)
+    HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+  else
+    HIP_CHECK(hipMemcpyPeerAsync(dst, to->device, src, from->device, bytes, st));
+}
+// flow.cpp: eegfx_confusion_counts' verdict on a device count (bad label, then fewer than two
+// actual classes), and its cells as counts.
+void confusion_verdict(const ConfusionOut& h, int64_t counts[4]);
 // tree_driver.cpp: the binned rows of a tree or forest call.  Host: the threshold table `tab`
 // (int32 flags[4], nthr[d], double thr[d][T]); device: the same table, bins uint8 [n][d], slot
 // int32 [n] = 0, label uint8 [n], and the scratch allocation for the histograms.

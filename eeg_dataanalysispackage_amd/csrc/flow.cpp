@@ -1,11 +1,12 @@
 // flow.cpp -- the train/test flow's glue of the eegfx C ABI (eegfx_java_shuffle,
-// eegfx_gather_rows, eegfx_confusion_counts) over the kernels of flow.hip; eegfx_odp_split
-// (odp.cpp) is built from the same pieces.  PipelineBuilder.java:170-223: shuffle both lists with
+// eegfx_split_shard_plan, eegfx_gather_rows, eegfx_confusion_counts) over the kernels of flow.hip;
+// eegfx_odp_split and eegfx_odp_split_sharded (odp.cpp) are built from the same pieces.  PipelineBuilder.java:170-223: shuffle both lists with
 // Random(1), split 70/30, train, test, report four counters.
 #include <cstring>
 #include <vector>
 
 #include "ctx.h"
+#include "split_plan.h"
 
 namespace eegfx {
 
@@ -64,6 +65,16 @@ void gather_check(eegfx_ctx* ctx, int slots, int64_t n_src) {
            (long long)n_src);
 }
 
+void confusion_verdict(const ConfusionOut& h, int64_t counts[4]) {
+  if (h.seen & kSeenOther) fail(EEGFX_EINVAL, "%s", kBadLabels);
+  // MulticlassMetrics' matrix has one row per actual class: with fewer than two the
+  // reference's cm[1] throws (LogisticRegressionClassifier.java:131)
+  if (h.seen != (kSeenZero | kSeenOne))
+    fail(EEGFX_ERANGE, "Index 1 out of bounds for length %d: the labels hold %s",
+         h.seen ? 1 : 0, h.seen ? "one class" : "no class");
+  for (int k = 0; k < 4; ++k) counts[k] = (int64_t)h.cell[k];
+}
+
 }  // namespace eegfx
 
 extern "C" {
@@ -73,6 +84,29 @@ int eegfx_java_shuffle(int64_t n, int64_t seed, int64_t* perm) {
     const std::vector<int64_t> p = java_shuffle(n, seed);
     if (n > 0 && !perm) fail(EEGFX_EINVAL, "null argument");
     if (n > 0) memcpy(perm, p.data(), sizeof(int64_t) * (size_t)n);
+  });
+}
+
+int eegfx_split_shard_plan(int64_t n, int64_t first, int64_t count, int64_t seed,
+                           double train_fraction, int64_t* idx, int64_t* pos, int64_t* n_train,
+                           int64_t* n_test) {
+  return guarded([&] {
+    const std::vector<int64_t> perm = java_shuffle(n, seed);
+    if (!n_train || !n_test) fail(EEGFX_EINVAL, "null argument");
+    if (!(train_fraction >= 0.0 && train_fraction <= 1.0))
+      fail(EEGFX_EINVAL, "train_fraction %g outside [0, 1]", train_fraction);
+    if (first < 0 || count < 0 || first > n || count > n - first)
+      fail(EEGFX_EINVAL, "rows [%lld, %lld + %lld) outside [0, %lld]", (long long)first,
+           (long long)first, (long long)count, (long long)n);
+    if (count > 0 && (!idx || !pos)) fail(EEGFX_EINVAL, "null idx / pos");
+    const SplitShardPlan s = split_shard_plan(perm.data(), n, (int64_t)((double)n * train_fraction),
+                                              first, count);
+    *n_train = s.n_train;
+    *n_test = s.n_test;
+    if (count > 0) {
+      memcpy(idx, s.idx.data(), sizeof(int64_t) * (size_t)count);
+      memcpy(pos, s.pos.data(), sizeof(int64_t) * (size_t)count);
+    }
   });
 }
 
@@ -119,13 +153,7 @@ int eegfx_confusion_counts(eegfx_ctx* ctx, const double* pred, const double* lab
       HIP_CHECK(hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
       ctx->drain();
     }
-    if (h.seen & kSeenOther) fail(EEGFX_EINVAL, "%s", kBadLabels);
-    // MulticlassMetrics' matrix has one row per actual class: with fewer than two the
-    // reference's cm[1] throws (LogisticRegressionClassifier.java:131)
-    if (h.seen != (kSeenZero | kSeenOne))
-      fail(EEGFX_ERANGE, "Index 1 out of bounds for length %d: the labels hold %s",
-           h.seen ? 1 : 0, h.seen ? "one class" : "no class");
-    for (int k = 0; k < 4; ++k) counts[k] = (int64_t)h.cell[k];
+    confusion_verdict(h, counts);
   });
 }
 

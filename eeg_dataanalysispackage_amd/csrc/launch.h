@@ -179,6 +179,19 @@ hipError_t launch_lr_iteration(hipStream_t st, int grad, const double* X, const 
 hipError_t launch_lr_predict(hipStream_t st, int grad, const double* X, int64_t n, int d,
                              const double* w, double intercept, double threshold,
                              int use_threshold, double* out);
+// The pieces of an iteration, for the driver over several shards (sharded.cpp): the gradient
+// partials [G][d] of the rows X[n] (pos: the bit of row r in `mask` is pos[r], nullptr: r); those
+// partials as one d-vector `out`, in lr_update_kernel's order of summation; the update from G
+// partials with `count` rows as the divisor; the empty sample's step.
+hipError_t launch_lr_gradient(hipStream_t st, int grad, const double* X, const double* y,
+                              int64_t n, int d, const uint32_t* mask, const int64_t* pos,
+                              const LrState* state, double* partial, int G);
+hipError_t launch_lr_fold(hipStream_t st, const double* partial, int G, int d,
+                          const LrState* state, double* out);
+hipError_t launch_lr_update(hipStream_t st, const double* partial, int G, int64_t count, int d,
+                            LrState* state, double step_size, double reg, double tol,
+                            int max_iter);
+hipError_t launch_lr_skip(hipStream_t st, LrState* state, int max_iter);
 
 
 // blocks for `items` at `per_block` a block: at least 1, at most `cap` (grid-stride kernels)
@@ -262,6 +275,12 @@ struct ConfusionOut {          // zeroed by the caller
 };
 hipError_t launch_confusion(hipStream_t st, const double* pred, const double* labels, int64_t n,
                             ConfusionOut* out);
+// logreg.hip lr_count_kernel: the rows X[n] scored as launch_lr_predict scores them and counted
+// against y[n] as launch_confusion counts, without the predictions in memory; `out` accumulates.
+constexpr int kLrCountMaxBlocks = 2048;  // 4 rows per workgroup and trip
+hipError_t launch_lr_count(hipStream_t st, int grad, const double* X, const double* y, int64_t n,
+                           int d, const double* w, double intercept, double threshold,
+                           int use_threshold, ConfusionOut* out);
 
 // nn.hip: the dense network of train_clf=nn (eegfx_nn_*).  The codes are
 // those of eegfx.h (EEGFX_NN_ACT_*, EEGFX_NN_LOSS_*, EEGFX_NN_UPD_*).

@@ -18,6 +18,12 @@
 // Every kernel first reads the flag, so the remaining iterations of a converged run are empty
 // launches.  Weights and the iteration state stay in device memory for the whole run.
 //
+// Over several shards (sharded.cpp) each shard runs the gradient kernel
+// on its rows and lr_fold_kernel sums its partials into one d-vector -- the loop lr_update_kernel
+// sums with, lr_fold_partials -- which the root's lr_update_kernel reads as one partial per shard.
+// lr_count_kernel is the test half: lr_predict_kernel's score met with the label in the cells of
+// flow.hip's confusion_kernel, no prediction stored.
+//
 // The same loop with HingeGradient is MLlib 1.6.2 SVMWithSGD (Classification/SVMClassifier.java:
 // 83-111: same updater, convergence test and defaults), scored by SVMModel.predict (:71, :114-137):
 // the gradient kernels take the gradient as a template parameter (grad_mult).
@@ -69,16 +75,25 @@ __device__ __forceinline__ double axpy_row(double mult, double x, double acc) {
   }
 }
 
-// Row r of iteration's sample (mask == nullptr: every row).
-__device__ __forceinline__ bool sampled(const uint32_t* __restrict__ mask, int64_t r) {
-  return !mask || ((mask[r >> 5] >> (r & 31)) & 1u);
+// Row r of iteration's sample (mask == nullptr: every row).  POS: the rows are a shard of a longer
+// list (eegfx_glm_sgd_train_sharded) and the row's bit is pos[r], not r: a flag of the kernel, so
+// that the instances the one-context entries launch are the code they were without it.
+template <bool POS>
+__device__ __forceinline__ bool sampled(const uint32_t* __restrict__ mask,
+                                        const int64_t* __restrict__ pos, int64_t r) {
+  if constexpr (POS) {
+    const int64_t b = pos[r];
+    return (mask[b >> 5] >> (b & 31)) & 1u;
+  } else {
+    return !mask || ((mask[r >> 5] >> (r & 31)) & 1u);
+  }
 }
 
-template <int KD, int GRAD>  // features per lane: d <= 64 * KD
+template <int KD, int GRAD, bool POS>  // features per lane: d <= 64 * KD
 __global__ __launch_bounds__(64 * kLrWaves) void lr_grad_kernel(
     const double* __restrict__ X, const double* __restrict__ y, int64_t n, int d,
-    const uint32_t* __restrict__ mask, const LrState* __restrict__ st,
-    double* __restrict__ partial) {
+    const uint32_t* __restrict__ mask, const int64_t* __restrict__ pos,
+    const LrState* __restrict__ st, double* __restrict__ partial) {
   if (st->converged) return;
   __shared__ double acc_s[kLrWaves][64 * KD];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -92,7 +107,7 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad_kernel(
   }
   const int64_t stride = (int64_t)gridDim.x * kLrWaves;
   for (int64_t r = (int64_t)blockIdx.x * kLrWaves + w; r < n; r += stride) {
-    if (!sampled(mask, r)) continue;  // wave-uniform: one row per wave
+    if (!sampled<POS>(mask, pos, r)) continue;  // wave-uniform: one row per wave
     const double* row = X + r * d;
     double x[KD];
     double dot = 0.0;
@@ -138,11 +153,11 @@ __device__ __forceinline__ double row16_sum(double v) {
 
 // d <= 16*FPL: a row is owned by the 16 lanes of one DPP row (lane j: features j, j+16, ...), so
 // a wave works on 4 rows at once, two such groups in flight.
-template <int FPL, int GRAD>
+template <int FPL, int GRAD, bool POS>
 __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
     const double* __restrict__ X, const double* __restrict__ y, int64_t n, int d,
-    const uint32_t* __restrict__ mask, const LrState* __restrict__ st,
-    double* __restrict__ partial) {
+    const uint32_t* __restrict__ mask, const int64_t* __restrict__ pos,
+    const LrState* __restrict__ st, double* __restrict__ partial) {
   if (st->converged) return;
   __shared__ double acc_s[kLrWaves * 4][16 * FPL];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -173,7 +188,7 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
       const int64_t r = r0 + 4 * u + q;
       dot[u] = 0.0;
       if constexpr (GRAD == 0) {
-        const bool ok = r < n && sampled(mask, r);
+        const bool ok = r < n && sampled<POS>(mask, pos, r);
         const double* row = X + (ok ? r : 0) * d;
 #pragma unroll
         for (int k = 0; k < FPL; ++k) {
@@ -197,7 +212,7 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const double m = row16_sum(dot[u]);
-      const bool ok = r0 + 4 * u + q < n && sampled(mask, r0 + 4 * u + q);
+      const bool ok = r0 + 4 * u + q < n && sampled<POS>(mask, pos, r0 + 4 * u + q);
       mult[u] = ok ? grad_mult<GRAD>(m, yy[u]) : 0.0;
       msum += m;  // non-finite as soon as one margin is
     }
@@ -218,7 +233,7 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
             dt = __builtin_fma(x[u][k], wv[k], dt);
           }
           const double m = row16_sum(dt);
-          const bool ok = r0 + 4 * u + q < n && sampled(mask, r0 + 4 * u + q);
+          const bool ok = r0 + 4 * u + q < n && sampled<POS>(mask, pos, r0 + 4 * u + q);
           const double mu = ok ? grad_mult<GRAD>(m, yy[u]) : 0.0;
 #pragma unroll
           for (int k = 0; k < FPL; ++k) acc[k] = axpy_row<GRAD>(mu, x[u][k], acc[k]);
@@ -243,17 +258,13 @@ __global__ __launch_bounds__(64 * kLrWaves) void lr_grad16_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void lr_update_kernel(const double* __restrict__ partial, int G,
-                                                        int64_t n, int d, double step_size,
-                                                        double reg, double tol, int max_iter,
-                                                        LrState* __restrict__ st) {
-  if (st->converged) return;
-  __shared__ double red[2][256];
-  __shared__ double gs[256];
-  const int it = st->iter + 1;
-  const double step = step_size / sqrt((double)it);
-  // partial sums: thread (j, f) adds workgroups b = j, j+K, ... (K groups of d threads), then the
-  // K group sums are added in group order -- a fixed order, so runs are bit-reproducible
+// The sum of G partial gradients [G][d], feature by feature, by one workgroup of 256 threads:
+// thread (j, f) adds partials b = j, j+K, ... (K groups of d threads), then the K group sums are
+// added in group order -- a fixed order, so runs are bit-reproducible.  each(f, g) receives the sum
+// of feature f on the thread that owns it.  gs: 256 doubles of LDS.
+template <typename Each>
+__device__ __forceinline__ void lr_fold_partials(const double* __restrict__ partial, int G, int d,
+                                                 double* gs, Each&& each) {
   const int K = d <= 128 ? (int)blockDim.x / d : 1;
   if (K > 1) {
     const int t = threadIdx.x, jj = t / d, f = t - jj * d;
@@ -269,7 +280,6 @@ __global__ __launch_bounds__(256) void lr_update_kernel(const double* __restrict
     }
     __syncthreads();
   }
-  double diff2 = 0.0, norm2 = 0.0;
   for (int f = threadIdx.x; f < d; f += blockDim.x) {
     double g = 0.0;
     if (K > 1) {
@@ -277,6 +287,31 @@ __global__ __launch_bounds__(256) void lr_update_kernel(const double* __restrict
     } else {
       for (int b = 0; b < G; ++b) g += partial[(int64_t)b * d + f];
     }
+    each(f, g);
+  }
+}
+
+// A shard's G workgroup partials as one d-vector (eegfx_glm_sgd_train_sharded): the vector the
+// root's lr_update_kernel then reads as one partial of its own.
+__global__ __launch_bounds__(256) void lr_fold_kernel(const double* __restrict__ partial, int G,
+                                                      int d, const LrState* __restrict__ st,
+                                                      double* __restrict__ out) {
+  if (st->converged) return;
+  __shared__ double gs[256];
+  lr_fold_partials(partial, G, d, gs, [&](int f, double g) { out[f] = g; });
+}
+
+__global__ __launch_bounds__(256) void lr_update_kernel(const double* __restrict__ partial, int G,
+                                                        int64_t n, int d, double step_size,
+                                                        double reg, double tol, int max_iter,
+                                                        LrState* __restrict__ st) {
+  if (st->converged) return;
+  __shared__ double red[2][256];
+  __shared__ double gs[256];
+  const int it = st->iter + 1;
+  const double step = step_size / sqrt((double)it);
+  double diff2 = 0.0, norm2 = 0.0;
+  lr_fold_partials(partial, G, d, gs, [&](int f, double g) {
     g = g / (double)n;
     const double old = st->w[f];
     double nw = old * (1.0 - step * reg);
@@ -284,7 +319,7 @@ __global__ __launch_bounds__(256) void lr_update_kernel(const double* __restrict
     st->w[f] = nw;
     diff2 += (old - nw) * (old - nw);
     norm2 += nw * nw;
-  }
+  });
   red[0][threadIdx.x] = diff2;
   red[1][threadIdx.x] = norm2;
   __syncthreads();
@@ -315,7 +350,27 @@ __global__ void lr_skip_kernel(int max_iter, LrState* __restrict__ st) {
 }
 
 // KIND 0: LogisticRegressionModel.predictPoint (score = sigmoid(w.x + b)); KIND 1:
-// SVMModel.predictPoint (score = the margin w.x + b).  out = score > threshold ? 1 : 0, or the score.
+// SVMModel.predictPoint (score = the margin w.x + b).  The score of row r, in every lane of the
+// wave that computes it.
+template <int KD, int KIND>
+__device__ __forceinline__ double lr_score(const double* __restrict__ X, int64_t r, int d,
+                                           const double* __restrict__ wt, double intercept,
+                                           int lane) {
+  double dot = 0.0;
+#pragma unroll
+  for (int k = 0; k < KD; ++k) {
+    const int f = lane + 64 * k;
+    if (f < d) dot = __builtin_fma(X[r * d + f], wt[f], dot);
+  }
+  dot = wave_sum(dot);
+  const double margin = dot + intercept;
+  return KIND == 0 ? 1.0 / (1.0 + exp(-margin)) : margin;
+}
+// What the model predicts from a score: score > threshold ? 1 : 0, or the score itself.
+__device__ __forceinline__ double lr_decide(double score, double threshold, int use_threshold) {
+  return use_threshold ? (score > threshold ? 1.0 : 0.0) : score;
+}
+
 template <int KD, int KIND>
 __global__ __launch_bounds__(256) void lr_predict_kernel(const double* __restrict__ X, int64_t n,
                                                          int d, const double* __restrict__ wt,
@@ -325,17 +380,53 @@ __global__ __launch_bounds__(256) void lr_predict_kernel(const double* __restric
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n) return;
-  double dot = 0.0;
-#pragma unroll
-  for (int k = 0; k < KD; ++k) {
-    const int f = lane + 64 * k;
-    if (f < d) dot = __builtin_fma(X[r * d + f], wt[f], dot);
+  const double score = lr_score<KD, KIND>(X, r, d, wt, intercept, lane);
+  if (lane == 0) out[r] = lr_decide(score, threshold, use_threshold);
+}
+
+// Score and count in one pass (eegfx_glm_count_sharded): row r of a trip goes to wave r mod (4 G),
+// which scores it as lr_predict_kernel does; the prediction meets the row's label in the cells of
+// confusion_kernel (flow.hip: tp, tn, "fp" = actual 1 / predicted 0, "fn"; a prediction that is
+// neither 0.0 nor 1.0 is counted nowhere).  Every lane of a wave holds the wave's counts; the four
+// waves are added in LDS and the workgroup adds its non-zero sums to out with one atomic each.
+template <int KD, int KIND>
+__global__ __launch_bounds__(256) void lr_count_kernel(const double* __restrict__ X,
+                                                       const double* __restrict__ y, int64_t n,
+                                                       int d, const double* __restrict__ wt,
+                                                       double intercept, double threshold,
+                                                       int use_threshold,
+                                                       ConfusionOut* __restrict__ out) {
+  __shared__ unsigned long long cell_s[4][4];
+  __shared__ unsigned seen_s[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  unsigned long long cell[4] = {0, 0, 0, 0};
+  unsigned seen = 0;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < n; r += stride) {
+    const double p =
+        lr_decide(lr_score<KD, KIND>(X, r, d, wt, intercept, lane), threshold, use_threshold);
+    const double a = y[r];
+    const bool a1 = a == 1.0, a0 = a == 0.0;
+    seen |= a1 ? kSeenOne : a0 ? kSeenZero : kSeenOther;
+    const bool p1 = p == 1.0, p0 = p == 0.0;
+    cell[0] += a1 && p1;
+    cell[1] += a0 && p0;
+    cell[2] += a1 && p0;
+    cell[3] += a0 && p1;
   }
-  dot = wave_sum(dot);
   if (lane == 0) {
-    const double margin = dot + intercept;
-    const double score = KIND == 0 ? 1.0 / (1.0 + exp(-margin)) : margin;
-    out[r] = use_threshold ? (score > threshold ? 1.0 : 0.0) : score;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cell_s[w][k] = cell[k];
+    seen_s[w] = seen;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    const unsigned long long s = cell_s[0][k] + cell_s[1][k] + cell_s[2][k] + cell_s[3][k];
+    if (s) atomicAdd(&out->cell[k], s);
+  } else if (threadIdx.x == 4) {
+    const unsigned s = seen_s[0] | seen_s[1] | seen_s[2] | seen_s[3];
+    if (s) atomicOr(&out->seen, s);
   }
 }
 
@@ -367,46 +458,62 @@ int lr_grid(int64_t n) {
     CALL;                     \
     break;
 
-template <int GRAD>
-static hipError_t lr_iteration(hipStream_t st, const double* X, const double* y, int64_t n, int d,
-                               const uint32_t* mask, int64_t count, LrState* state,
-                               double* partial, int G, double step_size, double reg, double tol,
-                               int max_iter) {
-  if (count == 0) {
-    hipLaunchKernelGGL(dev::lr_skip_kernel, dim3(1), dim3(64), 0, st, max_iter, state);
-    return hipGetLastError();
-  }
+template <int GRAD, bool POS>
+static hipError_t lr_gradient(hipStream_t st, const double* X, const double* y, int64_t n, int d,
+                              const uint32_t* mask, const int64_t* pos, const LrState* state,
+                              double* partial, int G) {
+#define EEGFX_LR_GRAD(KERNEL, KD)                                                                \
+  EEGFX_LR_KD(KD, hipLaunchKernelGGL((dev::KERNEL<KD, GRAD, POS>), dim3(G), dim3(256), 0, st, X, \
+                                     y, n, d, mask, pos, state, partial))
   if (d <= 128) {
     const int fpl = (d + 15) / 16;
     switch (fpl <= 1 ? 1 : fpl <= 2 ? 2 : fpl <= 3 ? 3 : fpl <= 4 ? 4 : 8) {
-      EEGFX_LR_KD(1, hipLaunchKernelGGL((dev::lr_grad16_kernel<1, GRAD>), dim3(G), dim3(256), 0,
-                                        st, X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(2, hipLaunchKernelGGL((dev::lr_grad16_kernel<2, GRAD>), dim3(G), dim3(256), 0,
-                                        st, X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(3, hipLaunchKernelGGL((dev::lr_grad16_kernel<3, GRAD>), dim3(G), dim3(256), 0,
-                                        st, X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(4, hipLaunchKernelGGL((dev::lr_grad16_kernel<4, GRAD>), dim3(G), dim3(256), 0,
-                                        st, X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(8, hipLaunchKernelGGL((dev::lr_grad16_kernel<8, GRAD>), dim3(G), dim3(256), 0,
-                                        st, X, y, n, d, mask, state, partial))
+      EEGFX_LR_GRAD(lr_grad16_kernel, 1)
+      EEGFX_LR_GRAD(lr_grad16_kernel, 2)
+      EEGFX_LR_GRAD(lr_grad16_kernel, 3)
+      EEGFX_LR_GRAD(lr_grad16_kernel, 4)
+      EEGFX_LR_GRAD(lr_grad16_kernel, 8)
     }
   } else {
     const int kd = (d + 63) / 64;
     switch (kd <= 1 ? 1 : kd <= 2 ? 2 : kd <= 4 ? 4 : kd <= 8 ? 8 : 16) {
-      EEGFX_LR_KD(1, hipLaunchKernelGGL((dev::lr_grad_kernel<1, GRAD>), dim3(G), dim3(256), 0, st,
-                                        X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(2, hipLaunchKernelGGL((dev::lr_grad_kernel<2, GRAD>), dim3(G), dim3(256), 0, st,
-                                        X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(4, hipLaunchKernelGGL((dev::lr_grad_kernel<4, GRAD>), dim3(G), dim3(256), 0, st,
-                                        X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(8, hipLaunchKernelGGL((dev::lr_grad_kernel<8, GRAD>), dim3(G), dim3(256), 0, st,
-                                        X, y, n, d, mask, state, partial))
-      EEGFX_LR_KD(16, hipLaunchKernelGGL((dev::lr_grad_kernel<16, GRAD>), dim3(G), dim3(256), 0,
-                                         st, X, y, n, d, mask, state, partial))
+      EEGFX_LR_GRAD(lr_grad_kernel, 1)
+      EEGFX_LR_GRAD(lr_grad_kernel, 2)
+      EEGFX_LR_GRAD(lr_grad_kernel, 4)
+      EEGFX_LR_GRAD(lr_grad_kernel, 8)
+      EEGFX_LR_GRAD(lr_grad_kernel, 16)
     }
   }
+#undef EEGFX_LR_GRAD
+  return hipGetLastError();
+}
+
+hipError_t launch_lr_gradient(hipStream_t st, int grad, const double* X, const double* y,
+                              int64_t n, int d, const uint32_t* mask, const int64_t* pos,
+                              const LrState* state, double* partial, int G) {
+  // the hinge loop is full-batch: no mask, so no positions to look up
+  if (grad == kGradHinge) return lr_gradient<1, false>(st, X, y, n, d, nullptr, nullptr, state,
+                                                       partial, G);
+  return mask && pos ? lr_gradient<0, true>(st, X, y, n, d, mask, pos, state, partial, G)
+                     : lr_gradient<0, false>(st, X, y, n, d, mask, nullptr, state, partial, G);
+}
+
+hipError_t launch_lr_fold(hipStream_t st, const double* partial, int G, int d,
+                          const LrState* state, double* out) {
+  hipLaunchKernelGGL(dev::lr_fold_kernel, dim3(1), dim3(256), 0, st, partial, G, d, state, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_lr_update(hipStream_t st, const double* partial, int G, int64_t count, int d,
+                            LrState* state, double step_size, double reg, double tol,
+                            int max_iter) {
   hipLaunchKernelGGL(dev::lr_update_kernel, dim3(1), dim3(256), 0, st, partial, G, count, d,
                      step_size, reg, tol, max_iter, state);
+  return hipGetLastError();
+}
+
+hipError_t launch_lr_skip(hipStream_t st, LrState* state, int max_iter) {
+  hipLaunchKernelGGL(dev::lr_skip_kernel, dim3(1), dim3(64), 0, st, max_iter, state);
   return hipGetLastError();
 }
 
@@ -414,10 +521,10 @@ hipError_t launch_lr_iteration(hipStream_t st, int grad, const double* X, const 
                                int64_t n, int d, const uint32_t* mask, int64_t count,
                                LrState* state, double* partial, int G, double step_size,
                                double reg, double tol, int max_iter) {
-  return grad == kGradHinge ? lr_iteration<1>(st, X, y, n, d, mask, count, state, partial, G,
-                                              step_size, reg, tol, max_iter)
-                            : lr_iteration<0>(st, X, y, n, d, mask, count, state, partial, G,
-                                              step_size, reg, tol, max_iter);
+  if (count == 0) return launch_lr_skip(st, state, max_iter);
+  const hipError_t e = launch_lr_gradient(st, grad, X, y, n, d, mask, nullptr, state, partial, G);
+  if (e != hipSuccess) return e;
+  return launch_lr_update(st, partial, G, count, d, state, step_size, reg, tol, max_iter);
 }
 
 template <int KIND>
@@ -447,6 +554,36 @@ hipError_t launch_lr_predict(hipStream_t st, int grad, const double* X, int64_t 
   return grad == kGradHinge
              ? lr_predict<1>(st, X, n, d, w, intercept, threshold, use_threshold, out)
              : lr_predict<0>(st, X, n, d, w, intercept, threshold, use_threshold, out);
+}
+
+template <int KIND>
+static hipError_t lr_count(hipStream_t st, const double* X, const double* y, int64_t n, int d,
+                           const double* w, double intercept, double threshold, int use_threshold,
+                           ConfusionOut* out) {
+  const dim3 grid(grid_for(n, 4, kLrCountMaxBlocks));
+  const int kd = (d + 63) / 64;
+  switch (kd <= 1 ? 1 : kd <= 2 ? 2 : kd <= 4 ? 4 : kd <= 8 ? 8 : 16) {
+    EEGFX_LR_KD(1, hipLaunchKernelGGL((dev::lr_count_kernel<1, KIND>), grid, dim3(256), 0, st, X, y,
+                                      n, d, w, intercept, threshold, use_threshold, out))
+    EEGFX_LR_KD(2, hipLaunchKernelGGL((dev::lr_count_kernel<2, KIND>), grid, dim3(256), 0, st, X, y,
+                                      n, d, w, intercept, threshold, use_threshold, out))
+    EEGFX_LR_KD(4, hipLaunchKernelGGL((dev::lr_count_kernel<4, KIND>), grid, dim3(256), 0, st, X, y,
+                                      n, d, w, intercept, threshold, use_threshold, out))
+    EEGFX_LR_KD(8, hipLaunchKernelGGL((dev::lr_count_kernel<8, KIND>), grid, dim3(256), 0, st, X, y,
+                                      n, d, w, intercept, threshold, use_threshold, out))
+    EEGFX_LR_KD(16, hipLaunchKernelGGL((dev::lr_count_kernel<16, KIND>), grid, dim3(256), 0, st,
+                                       X, y, n, d, w, intercept, threshold, use_threshold, out))
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_lr_count(hipStream_t st, int grad, const double* X, const double* y, int64_t n,
+                           int d, const double* w, double intercept, double threshold,
+                           int use_threshold, ConfusionOut* out) {
+  if (n == 0) return hipSuccess;
+  return grad == kGradHinge
+             ? lr_count<1>(st, X, y, n, d, w, intercept, threshold, use_threshold, out)
+             : lr_count<0>(st, X, y, n, d, w, intercept, threshold, use_threshold, out);
 }
 #undef EEGFX_LR_KD
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "split_plan.h"
 
 using namespace eegfx;
 
@@ -62,6 +63,9 @@ struct eegfx_odp {
     int numerics = -1;  // numerics of d_features' rows; -1: loads under different numerics
   };
   std::vector<Shard> shards;
+  // eegfx_odp_split_sharded's buffers, one allocation per shard on its context: X [count][d] and
+  // y [count] (the training rows, then the test rows), then their positions int64 [count]
+  std::vector<void*> split_bufs;
 
   void put_file(const std::string& k, int32_t v) {
     for (auto& kv : files)
@@ -223,7 +227,18 @@ struct eegfx_odp {
   }
 
   // ---- the device pass: one worker per context -------------------------------------------------
+  void release_split() {
+    for (size_t r = 0; r < split_bufs.size() && r < ctxs.size(); ++r) {
+      if (!split_bufs[r]) continue;
+      (void)hipSetDevice(ctxs[r]->device);
+      (void)hipFreeAsync(split_bufs[r], ctxs[r]->stream);
+      (void)hipStreamSynchronize(ctxs[r]->stream);
+    }
+    split_bufs.clear();
+  }
+
   void release_shards() {
+    release_split();
     for (size_t r = 0; r < shards.size() && r < ctxs.size(); ++r) {
       Shard& s = shards[r];
       if (!s.d_epochs && !s.d_features) continue;
@@ -380,6 +395,7 @@ struct eegfx_odp {
   // loadData (:88-98): every exception is logged as fatal and swallowed; what was loaded stays.
   int load() {
     int64_t base = 0;  // the epochs held from earlier loads
+    release_split();
     int rc = guarded([&] {
       if (!sequential) reset();
       base = n_epochs;
@@ -591,11 +607,7 @@ int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_f
     ctx->drain();
     odp->feature_rows(skip, feature_size, [&](eegfx_ctx* c, const eegfx_odp::Shard& s,
                                               const double* from, size_t bytes) {
-      char* dst = rows + row * (size_t)s.first;
-      if (c->device == ctx->device)
-        HIP_CHECK(hipMemcpyAsync(dst, from, bytes, hipMemcpyDeviceToDevice, c->stream));
-      else
-        HIP_CHECK(hipMemcpyPeerAsync(dst, ctx->device, from, c->device, bytes, c->stream));
+      copy_between(rows + row * (size_t)s.first, ctx, from, c, bytes, c->stream);
     });
     ctx->activate();
     HIP_CHECK(hipMemcpyAsync(d_lab, odp->labels.data(), sizeof(double) * (size_t)n,
@@ -607,6 +619,64 @@ int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_f
     copy_back(ctx, X, d_X, row * (size_t)n, mem);
     copy_back(ctx, y, d_y, sizeof(double) * (size_t)n, mem);
     gather_check(ctx, 2, n);  // drains for both memory kinds
+  });
+}
+
+int eegfx_odp_split_sharded(eegfx_odp* odp, int64_t seed, double train_fraction, int32_t name,
+                            int32_t epoch_size, int32_t skip, int32_t feature_size,
+                            eegfx_split_shard* out) {
+  return guarded([&] {
+    if (!odp || !out) fail(EEGFX_EINVAL, "null argument");
+    if (!(train_fraction >= 0.0 && train_fraction <= 1.0))
+      fail(EEGFX_EINVAL, "train_fraction %g outside [0, 1]", train_fraction);
+    check_fe_params(3, name, epoch_size, skip, feature_size);
+    if (odp->ctxs.empty())
+      fail(EEGFX_EINVAL, "planning-only provider (no device context) holds no epochs");
+    odp->release_split();
+    const size_t k = odp->shards.size();
+    for (size_t r = 0; r < k; ++r) out[r] = eegfx_split_shard{(int32_t)r};
+    const int64_t n = odp->n_epochs;
+    if (n == 0) return;
+    const std::vector<int64_t> perm = java_shuffle(n, seed);
+    const int64_t cut = (int64_t)((double)n * train_fraction);  // (int)(data.size()*0.7)
+    const int d = 3 * feature_size;
+    std::vector<SplitShardPlan> plans(k);  // read by the uploads until the contexts are drained
+    odp->split_bufs.assign(k, nullptr);
+    odp->feature_rows(skip, feature_size, [&](eegfx_ctx* c, const eegfx_odp::Shard& s,
+                                              const double* rows, size_t) {
+      const size_t r = (size_t)(&s - odp->shards.data()), m = (size_t)s.count;
+      SplitShardPlan& pl = plans[r];
+      pl = split_shard_plan(perm.data(), n, cut, s.first, s.count);
+      HIP_CHECK(hipMallocAsync(&odp->split_bufs[r], sizeof(double) * m * (size_t)(d + 2),
+                               c->stream));
+      double* X = (double*)odp->split_bufs[r];
+      double* y = X + m * (size_t)d;
+      int64_t* pos = (int64_t*)(y + m);
+      int64_t* idx = (int64_t*)c->fl_idx.get(sizeof(int64_t) * m);
+      double* lab = (double*)c->fl_lab.get(sizeof(double) * m);
+      HIP_CHECK(hipMemcpyAsync(idx, pl.idx.data(), sizeof(int64_t) * m, hipMemcpyHostToDevice,
+                               c->stream));
+      HIP_CHECK(hipMemcpyAsync(pos, pl.pos.data(), sizeof(int64_t) * m, hipMemcpyHostToDevice,
+                               c->stream));
+      HIP_CHECK(hipMemcpyAsync(lab, &odp->labels[(size_t)s.first], sizeof(double) * m,
+                               hipMemcpyHostToDevice, c->stream));
+      run_gather_rows(c, rows, s.count, d, idx, s.count, X, 0);
+      run_gather_rows(c, lab, s.count, 1, idx, s.count, y, 1);
+      const int64_t a = pl.n_train, b = pl.n_test;
+      out[r].n_train = a;
+      out[r].n_test = b;
+      out[r].X_train = a ? X : nullptr;
+      out[r].y_train = a ? y : nullptr;
+      out[r].pos_train = a ? pos : nullptr;
+      out[r].X_test = b ? X + (size_t)a * d : nullptr;
+      out[r].y_test = b ? y + a : nullptr;
+      out[r].pos_test = b ? pos + a : nullptr;
+    });
+    for (size_t r = 0; r < k; ++r) {
+      if (odp->shards[r].count == 0) continue;
+      odp->ctxs[r]->activate();
+      gather_check(odp->ctxs[r], 2, odp->shards[r].count);
+    }
   });
 }
 

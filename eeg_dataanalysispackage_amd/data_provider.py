@@ -12,7 +12,8 @@ resident in HBM and ``getData()`` copies them back.
 ``OffLineDataProvider(args, contexts=[...])`` shards ``loadData()`` over several contexts (any mix
 of devices): one host planning pass, then one worker per context on its ``shard_range`` slice of
 the selected epochs.  The getters return the same rows in the same order; ``getShards()`` exposes
-each shard's resident device buffers (include/eegfx.h, eegfx_odp_create_multi).
+each shard's resident device buffers (include/eegfx.h, eegfx_odp_create_multi), and
+``splitShards()`` the train/test split of their feature rows, kept where the rows are.
 """
 from __future__ import annotations
 
@@ -64,6 +65,47 @@ class Shard:
     def __repr__(self):
         return (f"Shard(ctx_index={self.ctx_index}, device={self.device}, first={self.first}, "
                 f"count={self.count}, features_numerics={self.features_numerics})")
+
+
+class _IndexView(_DeviceView):
+    """A device array of int64 positions; otherwise a _DeviceView."""
+
+    def __init__(self, owner, address, shape):
+        super().__init__(owner, address, shape)
+        self.__cuda_array_interface__["typestr"] = "<i8"
+
+
+def _tensor(view, device):
+    """The view as a torch tensor on its device (no copy); an empty tensor for no rows."""
+    import torch
+    if 0 in view.shape:
+        dtype = torch.int64 if isinstance(view, _IndexView) else torch.float64
+        return torch.empty(view.shape, dtype=dtype, device=f"cuda:{device}")
+    return torch.as_tensor(view, device=f"cuda:{device}")
+
+
+class SplitShard:
+    """One shard's part of the train/test split (eegfx_split_shard), on context ``ctx_index``
+    (``context``): ``X_train`` (n_train, d), ``y_train`` (n_train) and ``pos_train`` (n_train,
+    int64: the position of each row in the training part of the shuffled list, increasing), and
+    the same for the test part.  Torch tensors over the provider's buffers, read-only by
+    contract, valid until the provider's next ``splitShards()``, ``loadData()`` or ``close()``."""
+
+    def __init__(self, owner, s, d, context):
+        self.ctx_index, self.context = int(s.ctx_index), context
+        self.n_train, self.n_test = int(s.n_train), int(s.n_test)
+        dev = context.device
+        for part, n in (("train", self.n_train), ("test", self.n_test)):
+            setattr(self, "X_" + part,
+                    _tensor(_DeviceView(owner, getattr(s, "X_" + part), (n, d)), dev))
+            setattr(self, "y_" + part,
+                    _tensor(_DeviceView(owner, getattr(s, "y_" + part), (n,)), dev))
+            setattr(self, "pos_" + part,
+                    _tensor(_IndexView(owner, getattr(s, "pos_" + part), (n,)), dev))
+
+    def __repr__(self):
+        return (f"SplitShard(ctx_index={self.ctx_index}, n_train={self.n_train}, "
+                f"n_test={self.n_test})")
 
 
 class OffLineDataProvider:
@@ -195,6 +237,20 @@ class OffLineDataProvider:
             call(ctx, X, y, _lib.MEM_HOST)
         cut = int(n_train.value)
         return X[:cut], y[:cut], X[cut:], y[cut:]
+
+    def splitShards(self, fe=None, seed: int = 1, train_fraction: float = 0.7
+                    ) -> List[SplitShard]:
+        """split() kept per shard (eegfx_odp_split_sharded): every shard's rows of the train and
+        the test part stay on the shard's own context, gathered there in the order of the shuffled
+        list, with their positions in it.  No feature row crosses a device boundary or reaches
+        host memory.  One SplitShard per context, in shard order."""
+        name, size, skip, fs = ((8, 512, 175, 16) if fe is None else
+                                (fe.NAME, fe.EPOCH_SIZE, fe.SKIP_SAMPLES, fe.FEATURE_SIZE))
+        k = int(lib().eegfx_odp_num_shards(self._h))
+        out = (_lib.SplitShard * max(1, k))()
+        check(lib().eegfx_odp_split_sharded(self._h, int(seed), float(train_fraction), int(name),
+                                            int(size), int(skip), int(fs), out))
+        return [SplitShard(self, out[i], 3 * int(fs), self._ctxs[i]) for i in range(k)]
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:

@@ -120,16 +120,29 @@ def gather_rows(ctx, src, idx, out=None):
     return out
 
 
-def run_train_clf(odp, classifier, fe=None):
+def run_train_clf(odp, classifier, fe=None, sharded=False):
     """PipelineBuilder.execute's train_clf branch (:170-223) for a loaded provider and one of the
     classifiers of :mod:`classification` (its config set by the caller): shuffle with Random(1),
     split 70/30, train, test; returns the ClassificationStatistics.  Epochs and feature rows stay
     on the device: what reaches the host is the model (and the tree's threshold sample) and the
     four counters.  ``fe``: a WaveletTransform, default (8, 512, 175, 16).  A classifier without
-    a context of its own runs on the provider's first one."""
+    a context of its own runs on the provider's first one.
+
+    ``sharded=True`` (train_clf=logreg and train_clf=svm): the rows of a provider over several
+    contexts stay on their shards (``splitShards``, ``trainShards``, ``testShards``): every shard
+    sums the gradient of its own rows, d doubles per shard and iteration move, and the counters
+    of the shards are added.  The other classifiers raise NotImplementedError."""
     from .feature_extraction import WaveletTransform
     if fe is None:
         fe = WaveletTransform(8, 512, 175, 16)
+    if sharded:
+        if not hasattr(classifier, "trainShards"):
+            raise NotImplementedError(f"{type(classifier).__name__} has no sharded training: "
+                                      "sharded=True serves train_clf=logreg and train_clf=svm")
+        classifier.setFeatureExtraction(fe)
+        split = odp.splitShards(fe)
+        classifier.trainShards(split)
+        return classifier.testShards(split)
     ctx = classifier._ctx
     if ctx is None and odp._ctxs:
         ctx = odp._ctxs[0]

@@ -646,6 +646,89 @@ int eegfx_odp_split(eegfx_odp* odp, eegfx_ctx* ctx, int64_t seed, double train_f
                     int32_t name, int32_t epoch_size, int32_t skip, int32_t feature_size,
                     double* X, double* y, int64_t* n_train, int mem);
 
+/* ---- the flow over the provider's shards: data-parallel SGD, rows in place --------------------
+ * eegfx_odp_split gathers every shard's rows on one context.  These entries leave them where they
+ * are: the split is kept per shard, LogisticRegressionWithSGD /
+ * SVMWithSGD sum their gradient where the rows live and move d doubles per shard and iteration,
+ * and the four counters are integers that add.
+ *
+ * eegfx_split_shard_plan (pure host function): the rows [first, first + count) of a list of n
+ * rows, within [0, n], as the split of eegfx_odp_split(seed, train_fraction) sees them.  With
+ * perm = eegfx_java_shuffle(n, seed) and cut = (int64_t)(n * train_fraction), the row
+ * first + idx[j] stands at position p of perm: j < *n_train lists the training rows (p < cut,
+ * pos[j] = p), j >= *n_train the *n_test test rows (pos[j] = p - cut), each part in increasing p.
+ * idx and pos hold `count` entries.
+ *
+ * eegfx_odp_split_sharded: out[s], s < eegfx_odp_num_shards, is shard s's part of that split, on
+ * its own context: the feature rows eegfx_odp_split takes for the same parameters (the resident
+ * `features` where they match, else the rows eegfx_odp_get_features computes) and the labels,
+ * gathered on the shard's stream, with the position of every row in its part.  No feature row
+ * crosses a device boundary or reaches host memory.  A pointer is NULL where its count is 0.  The
+ * provider owns the buffers: they stay valid until the next eegfx_odp_split_sharded,
+ * eegfx_odp_load_data or eegfx_odp_destroy.  Errors are those of eegfx_odp_split; n == 0 is
+ * EEGFX_OK with every count 0.  Every context has been drained when the call returns. */
+typedef struct {
+  int32_t ctx_index;         /* index into the provider's contexts                               */
+  int32_t pad;
+  int64_t n_train, n_test;
+  const double* X_train;     /* device, double[n_train][3 * feature_size]                        */
+  const double* y_train;     /* device, double[n_train]                                          */
+  const int64_t* pos_train;  /* device, position of each row in the training part, increasing    */
+  const double* X_test;      /* device, double[n_test][3 * feature_size]                         */
+  const double* y_test;
+  const int64_t* pos_test;   /* device, position of each row in the test part, increasing        */
+} eegfx_split_shard;
+int eegfx_split_shard_plan(int64_t n, int64_t first, int64_t count, int64_t seed,
+                           double train_fraction, int64_t* idx, int64_t* pos, int64_t* n_train,
+                           int64_t* n_test);
+int eegfx_odp_split_sharded(eegfx_odp* odp, int64_t seed, double train_fraction, int32_t name,
+                            int32_t epoch_size, int32_t skip, int32_t feature_size,
+                            eegfx_split_shard* out /* eegfx_odp_num_shards */);
+
+/* eegfx_glm_sgd_train_sharded: eegfx_logreg_sgd_train_partitioned (grad 0, LogisticGradient) or
+ * the hinge loop of eegfx_ext.h (grad 1, HingeGradient: full batch only) over rows that lie in
+ * n_shards pieces, each on its own context (any mix of devices; each context at most once, else
+ * EEGFX_EINVAL).  X [n][d], y [n] and pos [n] are device pointers on that context's device.  pos
+ * names the position of each row in the whole training list (distinct, within [0, sum of n));
+ * pos == NULL: the shard's rows follow those of the shards before it.  The positions only matter
+ * to mini_batch_fraction < 1, whose iteration i takes the rows of data.sample(false, f, 42 + i)
+ * over the whole list in num_partitions slices.  Shards with n == 0 take no part; the first shard
+ * with rows is the root.  Per iteration every shard sums the gradient of its rows on its own
+ * stream and sends d doubles to the root, the root updates and sends the state back: no host
+ * synchronisation, the ordering is stream events.  The sum over shards is taken in shard order,
+ * so runs are bit-reproducible; one shard gives the bits of the one-context entry.
+ * `weights` holds the initial weights on entry and the result on return (untouched by a failing
+ * call); arguments, bounds and errors are those of the one-context entry.  Every context has been
+ * drained when the call returns.
+ *
+ * eegfx_glm_shard_state: the training state the last eegfx_glm_sgd_train_sharded left on ctx --
+ * head = {iterations, flag (1: done), updates, 0} and the d weights: on every shard that took
+ * part it equals the root's, bit for bit.
+ *
+ * eegfx_glm_count_sharded: counts = {tp, tn, fp, fn} in eegfx_confusion_counts' reading, of the
+ * model's predictions (grad 0: LogisticRegressionModel, grad 1: SVMModel; threshold NaN: the raw
+ * score, as clearThreshold) against y over every shard's rows: what eegfx_logreg_predict followed
+ * by eegfx_confusion_counts gives on the rows together, without a prediction in memory.  pos is
+ * not read.  A label that is neither 0.0 nor 1.0 on any shard is EEGFX_EINVAL (checked first);
+ * labels of one class only over all shards, or no rows, are EEGFX_ERANGE.  Synchronises. */
+typedef struct {
+  eegfx_ctx* ctx;
+  const double* X;
+  const double* y;
+  const int64_t* pos;
+  int64_t n;
+} eegfx_glm_shard;
+int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t n_shards,
+                                int32_t d, int32_t num_iterations, double step_size,
+                                double reg_param, double mini_batch_fraction,
+                                double convergence_tol, int32_t num_partitions, double* weights,
+                                int32_t* iterations_run);
+int eegfx_available_processors(void);  /* eegfx_logreg_sgd_train's num_partitions: local[*] */
+int eegfx_glm_shard_state(eegfx_ctx* ctx, int32_t d, int32_t head[4], double* weights);
+int eegfx_glm_count_sharded(int grad, const eegfx_glm_shard* shards, int32_t n_shards, int32_t d,
+                            const double* weights, double intercept, double threshold,
+                            int64_t counts[4]);
+
 /* ---- train_clf=nn: the dense network of NeuralNetworkClassifier.java on the device ------------
  * DESIGN.md section 10.7 holds the definition; DL4J itself is not reproduced bit for bit (it
  * computes in float32 and draws its initial weights from ND4J's stream).  Everything is float64.
