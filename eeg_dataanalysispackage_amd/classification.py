@@ -20,7 +20,7 @@ its ``config_layer<i>_*`` keys, as DESIGN.md section 10.7 defines it (``eegfx_nn
 ``sgd_train_sharded`` / ``svm_sgd_train_sharded`` / ``count_sharded`` (and the classifiers'
 ``trainShards`` / ``testShards``) are the two SGD classifiers over rows that stay on the contexts of
 a sharded provider (``eegfx_glm_sgd_train_sharded`` / ``eegfx_glm_count_sharded``, DESIGN.md section
-10.11).
+10.11); one driver trains behind both sets of entries, a lone context being its one shard.
 Model save/load (Spark model directories) is out of scope.
 """
 from __future__ import annotations
@@ -71,11 +71,20 @@ def _predict_inputs(X):
     return X, out, _mem(X, out), n, d
 
 
+def _start_weights(d, initial_weights):
+    """The [d] array a train entry reads the initial weights from (None: zeros, as MLlib) and
+    writes the result to: the caller's own array is never written."""
+    w = (np.zeros(d) if initial_weights is None
+         else np.array(initial_weights, dtype=np.float64).copy())
+    if w.shape != (d,):
+        raise ValueError(f"initial_weights must be [{d}]")
+    return w
+
+
 def _train(entry, ctx: Context, X, y, num_iterations, step_size, reg_param, mini_batch_fraction,
            convergence_tol, initial_weights, num_partitions=None):
     X, y, n, d, mem = _train_inputs(X, y)
-    w = (np.zeros(d) if initial_weights is None
-         else np.array(initial_weights, dtype=np.float64).copy())
+    w = _start_weights(d, initial_weights)
     it = c_int32()
     # ordered after the torch work that produced X / y (Context._call), like every device call
     head = (ctx.handle, ptr(X), ptr(y), n, d, int(num_iterations), float(step_size),
@@ -200,10 +209,7 @@ def _train_sharded(grad, shards, num_iterations, step_size, reg_param, mini_batc
     arr, keep, d, order = _glm_shards(shards)
     if d is None:
         raise ValueError("no shards")
-    w = (np.zeros(d) if initial_weights is None
-         else np.array(initial_weights, dtype=np.float64).copy())
-    if w.shape != (d,):
-        raise ValueError(f"initial_weights must be [{d}]")
+    w = _start_weights(d, initial_weights)
     it = c_int32()
     parts = 1 if num_partitions is None else int(num_partitions)
     _call_sharded(order, lib().eegfx_glm_sgd_train_sharded, grad, arr, len(shards), d,
@@ -217,11 +223,12 @@ def sgd_train_sharded(shards, num_iterations: int = DEFAULT_NUM_ITERATIONS,
                       mini_batch_fraction: float = DEFAULT_MINI_BATCH_FRACTION,
                       convergence_tol: float = CONVERGENCE_TOL, initial_weights=None,
                       num_partitions: Optional[int] = None):
-    """sgd_train over rows that stay where they are (eegfx_glm_sgd_train_sharded).  ``shards``:
-    (context, X, y[, pos]) per shard, each context once; pos names the position of every row in
-    the whole training list (None: the shards' rows in shard order), which mini_batch_fraction < 1
-    samples as sgd_train does (num_partitions None: the processors available to the process).
-    Returns (weights, iterations_run); one shard gives sgd_train's bits."""
+    """sgd_train over rows that stay where they are (eegfx_glm_sgd_train_sharded: the driver
+    sgd_train runs with its context as the one shard).  ``shards``: (context, X, y[, pos]) per
+    shard, each context once; pos names the position of every row in the whole training list
+    (None: the shards' rows in shard order), the list mini_batch_fraction < 1 samples
+    (num_partitions None: the processors available to the process).
+    Returns (weights, iterations_run); one shard is sgd_train's run, bit for bit."""
     if num_partitions is None and mini_batch_fraction < 1.0:
         num_partitions = int(lib().eegfx_available_processors())
     return _train_sharded(0, shards, num_iterations, step_size, reg_param, mini_batch_fraction,
@@ -239,8 +246,9 @@ def svm_sgd_train_sharded(shards, num_iterations: int = DEFAULT_NUM_ITERATIONS,
 
 
 def shard_state(ctx: Context, d: int):
-    """(iterations, flag, updates, weights) of the training state the last sharded run left on
-    ``ctx`` (eegfx_glm_shard_state): on every shard that took part, the root's bits."""
+    """(iterations, flag, updates, weights) of the training state the last SGD run left on ``ctx``
+    (eegfx_glm_shard_state), whichever entry ran it: on every shard that took part, the root's
+    bits; after sgd_train / svm_sgd_train, the returned weights'."""
     head = np.zeros(4, dtype=np.int32)
     w = np.empty(d, dtype=np.float64)
     _lib.check(lib().eegfx_glm_shard_state(ctx.handle, int(d), ptr(head), ptr(w)))

@@ -1,5 +1,7 @@
-// classify.cpp -- the MLlib classifier drivers of the eegfx C ABI (eegfx_logreg_*, eegfx_svm_*,
-// eegfx_spark_sample) over the kernels of logreg.hip.
+// classify.cpp -- the one-context MLlib classifier entries of the eegfx C ABI (eegfx_logreg_*,
+// eegfx_svm_*, eegfx_spark_sample): the trainers' front door to the one SGD driver
+// (sharded.cpp glm_sgd_train_shards), whose argument checks and mini-batch masks live here, and the
+// predict driver over the kernels of logreg.hip.
 #include <sched.h>
 
 #include <algorithm>
@@ -87,65 +89,24 @@ void eegfx::draw_sgd_masks(int64_t n, double fraction, int num_partitions, int i
 // slices (spark_sample.h), drawn on the host (threads over iterations) as one bit mask per
 // iteration and uploaded before the iterations that read them.  The hinge loop of
 // eegfx_ext.h (SVMWithSGD) stays full-batch (outside the contract, not extended).
+// The entry's own refusals, then the driver of sharded.cpp with the context as its one shard.
 static int glm_sgd_train(int grad, eegfx_ctx* ctx, const double* X, const double* y, int64_t n,
                          int32_t d, int32_t num_iterations, double step_size, double reg_param,
                          double mini_batch_fraction, double convergence_tol,
                          int32_t num_partitions, double* weights, int32_t* iterations_run,
                          int mem) {
-  return guarded([&] {
+  const int refused = guarded([&] {
     if (!ctx || !weights) fail(EEGFX_EINVAL, "null argument");
     check_mem(mem);
     if (n < 1) fail(EEGFX_EINVAL, "empty training set");  // GeneralizedLinearAlgorithm: first()
     if (!X || !y) fail(EEGFX_EINVAL, "null X / y");
-    const bool sampled =
-        check_sgd_args(grad, d, num_iterations, mini_batch_fraction, num_partitions);
-    ctx->activate();
-    const auto [dX, dy] = stage_xy(ctx, X, y, n, d, mem);
-    const size_t sbytes = sizeof(LrState) + sizeof(double) * (size_t)d;
-    std::vector<uint8_t> hs(sbytes, 0);
-    LrState* h = (LrState*)hs.data();
-    h->converged = num_iterations == 0 ? 1 : 0;
-    memcpy(h->w, weights, sizeof(double) * (size_t)d);  // initial weights (zeros in MLlib)
-    LrState* st = (LrState*)ctx->lr_state.get(sbytes);
-    HIP_CHECK(hipMemcpyAsync(st, hs.data(), sbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(launch_lr_validate(ctx->stream, dy, n, st));
-    const int G = lr_grid(n);
-    double* part = (double*)ctx->lr_part.get(sizeof(double) * (size_t)G * d);
-    if (!sampled) {
-      for (int i = 0; i < num_iterations; ++i)
-        HIP_CHECK(launch_lr_iteration(ctx->stream, grad, dX, dy, n, d, nullptr, n, st, part, G,
-                                      step_size, reg_param, convergence_tol, num_iterations));
-    } else {
-      const int64_t words = (n + 31) / 32;
-      const int chunk = sgd_mask_chunk(n, num_iterations);
-      std::vector<uint32_t> masks((size_t)(chunk * words));
-      std::vector<int64_t> counts((size_t)chunk);
-      uint32_t* dmask = (uint32_t*)ctx->lr_mask.get(sizeof(uint32_t) * masks.size());
-      for (int i0 = 0; i0 < num_iterations; i0 += chunk) {
-        const int k = std::min(chunk, num_iterations - i0);
-        ctx->drain();  // the previous chunk's upload and iterations are done with both buffers
-        if (i0 > 0) {  // converged (or stopped): the remaining iterations would be skipped
-          int32_t conv = 0;
-          HIP_CHECK(hipMemcpyAsync(&conv, &st->converged, sizeof(conv), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-          HIP_CHECK(hipStreamSynchronize(ctx->stream));
-          if (conv != 0) break;
-        }
-        draw_sgd_masks(n, mini_batch_fraction, num_partitions, i0, k, masks.data(), counts.data());
-        HIP_CHECK(hipMemcpyAsync(dmask, masks.data(), sizeof(uint32_t) * (size_t)(k * words),
-                                 hipMemcpyHostToDevice, ctx->stream));
-        for (int j = 0; j < k; ++j)
-          HIP_CHECK(launch_lr_iteration(ctx->stream, grad, dX, dy, n, d, dmask + (size_t)j * words,
-                                        counts[j], st, part, G, step_size, reg_param,
-                                        convergence_tol, num_iterations));
-      }
-    }
-    HIP_CHECK(hipMemcpyAsync(hs.data(), st, sbytes, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->drain();
-    if (h->converged == 2) fail(EEGFX_EINVAL, "%s", kBadLabels);
-    memcpy(weights, h->w, sizeof(double) * (size_t)d);
-    if (iterations_run) *iterations_run = h->iter;
   });
+  if (refused != EEGFX_OK) return refused;
+  // the driver goes on with the ladder (check_sgd_args) and stages a host caller's rows behind it
+  const eegfx_glm_shard one = {ctx, X, y, nullptr, n};
+  return glm_sgd_train_shards(grad, &one, 1, d, num_iterations, step_size, reg_param,
+                              mini_batch_fraction, convergence_tol, num_partitions, weights,
+                              iterations_run, mem);
 }
 
 static int glm_predict(int grad, eegfx_ctx* ctx, const double* X, int64_t n, int32_t d,

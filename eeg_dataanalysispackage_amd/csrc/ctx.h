@@ -179,11 +179,11 @@ struct eegfx_ctx {
   // (train) or the predictions out (predict), and the int32 stimulus index per marker of
   // eegfx_plan_markers_device.
   DevBuf rows_x, row_vals;
-  // eegfx_logreg_* / eegfx_svm_*: LrState (train: state and weights; predict: the weights), the
-  // gradient partials, a chunk of mini-batch masks
+  // eegfx_logreg_* / eegfx_svm_* / eegfx_glm_*: LrState (train: state, weights and the label
+  // verdict behind them; predict: the weights), the gradient partials, a chunk of mini-batch masks
   DevBuf lr_state, lr_part, lr_mask;
-  // eegfx_glm_sgd_train_sharded: the root's [shards][d] slots / another shard's folded d-vector;
-  // the positions of a shard given without them
+  // more than one shard: the root's [shards][d] slots / another shard's folded d-vector; the
+  // positions of a shard given without them
   DevBuf lr_fold, lr_pos;
   // eegfx_dtree_train / eegfx_rforest_train (dt_bin_rows, grow_trees): threshold table, bins, slot
   // + label per row, one group's histograms (and the gathered split sample).  dt_nodes: records
@@ -398,7 +398,7 @@ inline void check_train_d(int32_t d) {
 inline void check_predict_dims(int64_t n, int32_t d) {
   if (n < 0 || d < 1 || d > kLrMaxFeatures) fail(EEGFX_EINVAL, "n=%lld d=%d", (long long)n, d);
 }
-// The training pair of glm_sgd_train and dt_bin_rows as the kernels read it.
+// The training pair of glm_sgd_train_shards and dt_bin_rows as the kernels read it.
 struct TrainXY {
   const double* X;
   const double* y;
@@ -424,10 +424,20 @@ void predict_frame(eegfx_ctx* ctx, const double* X, int64_t n, int32_t d, double
 
 // The processors this process may run on (classify.cpp): Spark local[*]'s defaultParallelism.
 int available_processors();
-// classify.cpp, shared by the one-context trainer and the one over shards (sharded.cpp): the
-// argument ladder past the null and row-count checks (returns whether the run is sampled); the
-// iterations whose masks are drawn and uploaded at a time; and the masks of iterations i0 + 1 ..
-// i0 + k over n rows ((n + 31) / 32 words each) with their row counts, drawn by threads.
+// sharded.cpp: the one GradientDescent driver, behind eegfx_glm_sgd_train_sharded and, with the
+// context as its one shard, behind the one-context entries (classify.cpp).  The caller has
+// checked the shards (contexts distinct, X / y there where n > 0); `weights` in and, on success
+// only, out.  mem: where every shard's X and y lie (pos: the device); host rows are staged on the
+// shard's context once the arguments have passed.  A guarded call of its own: returns the status.
+int glm_sgd_train_shards(int grad, const eegfx_glm_shard* shards, int32_t n_shards, int32_t d,
+                         int32_t num_iterations, double step_size, double reg_param,
+                         double mini_batch_fraction, double convergence_tol,
+                         int32_t num_partitions, double* weights, int32_t* iterations_run,
+                         int mem);
+// classify.cpp, the driver's: the argument ladder past the null and row-count checks (returns
+// whether the run is sampled); the iterations whose masks are drawn and uploaded at a time; and
+// the masks of iterations i0 + 1 .. i0 + k over n rows ((n + 31) / 32 words each) with their row
+// counts, drawn by threads.
 bool check_sgd_args(int grad, int32_t d, int32_t num_iterations, double mini_batch_fraction,
                     int32_t num_partitions);
 int sgd_mask_chunk(int64_t n, int num_iterations);

@@ -144,10 +144,11 @@ hipError_t launch_guard_fixup_raw(hipStream_t st, const void* raw, int fmt, int6
                                   const void* scratch, const Guard& g, double* out);
 
 // logreg.hip: MLlib LogisticRegressionWithSGD (full batch) on device.  State block: iteration
-// count, flag (0 running, 1 converged / done, 2 invalid labels), then the d weights.
+// count, flag (0 running, 1 converged / done), then the d weights.  lr_validate_kernel's verdict
+// goes to a header of its own behind them (sharded.cpp validity_word).
 struct LrState {
   int32_t iter;       // iterations done (GradientDescent's i - 1)
-  int32_t converged;  // 1: converged or done, 2: label validation failed
+  int32_t converged;  // 1: converged or done; in the validity word, 2: label validation failed
   int32_t updates;    // iterations that updated the weights (a non-empty mini-batch)
   int32_t pad;
   double w[];
@@ -170,19 +171,15 @@ hipError_t launch_lr_validate(hipStream_t st, const double* y, int64_t n, LrStat
 // kernel scores with the matching model (sigmoid of the margin / the margin itself).
 constexpr int kGradLogistic = 0;
 constexpr int kGradHinge = 1;
-// mask: iteration's mini-batch sample (bit r of word r / 32 = row r), nullptr = the whole batch;
-// count = its rows (the gradient's divisor; 0 = an empty sample: no update)
-hipError_t launch_lr_iteration(hipStream_t st, int grad, const double* X, const double* y,
-                               int64_t n, int d, const uint32_t* mask, int64_t count,
-                               LrState* state, double* partial, int G, double step_size,
-                               double reg, double tol, int max_iter);
 hipError_t launch_lr_predict(hipStream_t st, int grad, const double* X, int64_t n, int d,
                              const double* w, double intercept, double threshold,
                              int use_threshold, double* out);
-// The pieces of an iteration, for the driver over several shards (sharded.cpp): the gradient
-// partials [G][d] of the rows X[n] (pos: the bit of row r in `mask` is pos[r], nullptr: r); those
-// partials as one d-vector `out`, in lr_update_kernel's order of summation; the update from G
-// partials with `count` rows as the divisor; the empty sample's step.
+// The pieces of an iteration, put together by the one driver (sharded.cpp): the gradient partials
+// [G][d] of the rows X[n] (mask: the iteration's mini-batch sample, bit p of word p / 32 = row p
+// of the whole list, nullptr = the whole batch; pos: row r is row pos[r] of the list, nullptr: r);
+// with more than one shard, those partials as one d-vector `out`, in lr_update_kernel's order of
+// summation; the update from G partials with `count` > 0 rows, the sample's, as the divisor; the
+// step of an empty sample (count 0: no gradient, no update).
 hipError_t launch_lr_gradient(hipStream_t st, int grad, const double* X, const double* y,
                               int64_t n, int d, const uint32_t* mask, const int64_t* pos,
                               const LrState* state, double* partial, int G);

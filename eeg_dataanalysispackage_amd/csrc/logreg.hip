@@ -517,16 +517,6 @@ hipError_t launch_lr_skip(hipStream_t st, LrState* state, int max_iter) {
   return hipGetLastError();
 }
 
-hipError_t launch_lr_iteration(hipStream_t st, int grad, const double* X, const double* y,
-                               int64_t n, int d, const uint32_t* mask, int64_t count,
-                               LrState* state, double* partial, int G, double step_size,
-                               double reg, double tol, int max_iter) {
-  if (count == 0) return launch_lr_skip(st, state, max_iter);
-  const hipError_t e = launch_lr_gradient(st, grad, X, y, n, d, mask, nullptr, state, partial, G);
-  if (e != hipSuccess) return e;
-  return launch_lr_update(st, partial, G, count, d, state, step_size, reg, tol, max_iter);
-}
-
 template <int KIND>
 static hipError_t lr_predict(hipStream_t st, const double* X, int64_t n, int d, const double* w,
                              double intercept, double threshold, int use_threshold, double* out) {

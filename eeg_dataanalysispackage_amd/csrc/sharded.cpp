@@ -1,6 +1,7 @@
-// sharded.cpp -- the MLlib SGD classifiers over rows that stay on several contexts
+// sharded.cpp -- the MLlib SGD classifiers' one GradientDescent driver (glm_sgd_train_shards), over
+// the kernels of logreg.hip, and the entries over rows that stay on several contexts
 // (eegfx_glm_sgd_train_sharded, eegfx_glm_shard_state, eegfx_glm_count_sharded; DESIGN.md section
-// 10.11), over the kernels of logreg.hip and beside the one-context drivers of classify.cpp.
+// 10.11).  The one-context entries of classify.cpp hand the driver their context as its one shard.
 //
 // GradientDescent's iteration is a sum over rows followed by a d-vector update, so it shards
 // exactly: every shard sums the gradient of its own rows (the gradient kernel, then lr_fold_kernel:
@@ -12,6 +13,9 @@
 //   shard s, iteration i   [wait back(i-1)]  gradient  fold  copy to slot s  record sent_s(i)
 //   root,    iteration i   gradient  fold into slot 0  wait sent_s(i), all s  update
 //                          copy the state to every s  record back(i)
+// A lone shard needs none of that: its iteration is the gradient kernel and lr_update_kernel on its
+// own G partials -- the sum the fold would have taken, in lr_fold_partials' order either way -- with
+// no fold, slot buffer, event or copy.
 // Hazards.  Slot s is rewritten by shard s's copy of iteration i+1, which its stream runs after
 // back(i), recorded after the update of iteration i read the slot.  Shard s's state copy is
 // overwritten by the root after the root's stream waited on sent_s(i), recorded after shard s's
@@ -44,7 +48,7 @@ struct Active {  // a shard with rows
   int G;
   LrState* st;
   double* part;
-  double* fold;        // root: the slots [active][d]; else this shard's d-vector
+  double* fold;        // root: the slots [active][d]; else this shard's d-vector; lone: none
   uint32_t* mask;
   hipEvent_t sent[kEventRing];
 };
@@ -91,18 +95,13 @@ void drained_on_failure(const std::vector<Active>& act, F&& body) {
 }
 
 }  // namespace
-}  // namespace eegfx
 
-extern "C" {
-
-int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t n_shards,
-                                int32_t d, int32_t num_iterations, double step_size,
-                                double reg_param, double mini_batch_fraction,
-                                double convergence_tol, int32_t num_partitions, double* weights,
-                                int32_t* iterations_run) {
+int glm_sgd_train_shards(int grad, const eegfx_glm_shard* shards, int32_t n_shards, int32_t d,
+                         int32_t num_iterations, double step_size, double reg_param,
+                         double mini_batch_fraction, double convergence_tol,
+                         int32_t num_partitions, double* weights, int32_t* iterations_run,
+                         int mem) {
   return guarded([&] {
-    if (!weights) fail(EEGFX_EINVAL, "null argument");
-    check_shards(shards, n_shards);
     int64_t n_total = 0;
     for (int32_t s = 0; s < n_shards; ++s) n_total += shards[s].n;
     if (n_total < 1) fail(EEGFX_EINVAL, "empty training set");
@@ -128,13 +127,18 @@ int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t
       for (int32_t s = 0; s < n_shards; offset += shards[s++].n) {
         const eegfx_glm_shard& in = shards[s];
         if (in.n == 0) continue;
-        Active a = {in.ctx, in.X, in.y, in.pos, in.n, lr_grid(in.n)};
-        eegfx_ctx* c = a.ctx;
         const bool root = act.empty();
+        act.push_back({in.ctx, in.X, in.y, in.pos, in.n, lr_grid(in.n)});  // drained from here on
+        Active& a = act.back();
+        eegfx_ctx* c = a.ctx;
         c->activate();
+        const TrainXY xy = stage_xy(c, in.X, in.y, in.n, d, mem);
+        a.X = xy.X;
+        a.y = xy.y;
         a.st = (LrState*)c->lr_state.get(sbytes + vbytes);
         a.part = (double*)c->lr_part.get(sizeof(double) * (size_t)a.G * d);
-        a.fold = (double*)c->lr_fold.get(sizeof(double) * (size_t)d * (root ? n_active : 1));
+        if (n_active > 1)
+          a.fold = (double*)c->lr_fold.get(sizeof(double) * (size_t)d * (root ? n_active : 1));
         a.mask = sampled ? (uint32_t*)c->lr_mask.get(sizeof(uint32_t) * (size_t)(chunk * words))
                          : nullptr;
         if (sampled && !a.pos && offset > 0) {
@@ -149,7 +153,6 @@ int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t
                                  c->stream));
         HIP_CHECK(launch_lr_validate(c->stream, a.y, a.n, validity_word(a.st, d)));
         for (hipEvent_t& e : a.sent) e = root ? nullptr : events.make(c);
-        act.push_back(a);
       }
       const Active& root = act[0];
       const size_t k_act = act.size();
@@ -178,6 +181,7 @@ int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t
             const uint32_t* mask = sampled ? a.mask + (size_t)j * words : nullptr;
             HIP_CHECK(launch_lr_gradient(st, grad, a.X, a.y, a.n, d, mask, a.pos, a.st, a.part,
                                          a.G));
+            if (k_act == 1) break;  // a lone shard: the update reads a.part as it is
             HIP_CHECK(launch_lr_fold(st, a.part, a.G, d, a.st, s == 0 ? root.fold : a.fold));
             if (s == 0) continue;
             copy_between(root.fold + s * (size_t)d, root.ctx, a.fold, a.ctx,
@@ -186,9 +190,11 @@ int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t
           }
           const hipStream_t st = on(root);
           for (size_t s = 1; s < k_act; ++s) HIP_CHECK(hipStreamWaitEvent(st, act[s].sent[ring], 0));
-          HIP_CHECK(launch_lr_update(st, root.fold, (int)k_act, count, d, root.st, step_size,
-                                     reg_param, convergence_tol, num_iterations));
-        } else {
+          const bool lone = k_act == 1;  // its own partials: the same sum without the fold
+          HIP_CHECK(launch_lr_update(st, lone ? root.part : root.fold, lone ? root.G : (int)k_act,
+                                     count, d, root.st, step_size, reg_param, convergence_tol,
+                                     num_iterations));
+        } else {  // an empty sample: the iteration counts, nothing else moves
           HIP_CHECK(launch_lr_skip(on(root), root.st, num_iterations));
         }
         if (k_act == 1) return;
@@ -244,6 +250,25 @@ int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t
     memcpy(weights, r->w, sizeof(double) * (size_t)d);
     if (iterations_run) *iterations_run = r->iter;
   });
+}
+
+}  // namespace eegfx
+
+extern "C" {
+
+int eegfx_glm_sgd_train_sharded(int grad, const eegfx_glm_shard* shards, int32_t n_shards,
+                                int32_t d, int32_t num_iterations, double step_size,
+                                double reg_param, double mini_batch_fraction,
+                                double convergence_tol, int32_t num_partitions, double* weights,
+                                int32_t* iterations_run) {
+  const int refused = guarded([&] {
+    if (!weights) fail(EEGFX_EINVAL, "null argument");
+    check_shards(shards, n_shards);
+  });
+  if (refused != EEGFX_OK) return refused;
+  return glm_sgd_train_shards(grad, shards, n_shards, d, num_iterations, step_size, reg_param,
+                              mini_batch_fraction, convergence_tol, num_partitions, weights,
+                              iterations_run, EEGFX_MEM_DEVICE);
 }
 
 int eegfx_glm_shard_state(eegfx_ctx* ctx, int32_t d, int32_t head[4], double* weights) {

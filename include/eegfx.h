@@ -701,9 +701,10 @@ int eegfx_odp_split_sharded(eegfx_odp* odp, int64_t seed, double train_fraction,
  * call); arguments, bounds and errors are those of the one-context entry.  Every context has been
  * drained when the call returns.
  *
- * eegfx_glm_shard_state: the training state the last eegfx_glm_sgd_train_sharded left on ctx --
- * head = {iterations, flag (1: done), updates, 0} and the d weights: on every shard that took
- * part it equals the root's, bit for bit.
+ * eegfx_glm_shard_state: the training state the last eegfx_glm_sgd_train_sharded, or the last
+ * one-context train entry (one shard of its own), left on ctx -- head = {iterations, flag (1:
+ * done), updates, 0} and the d weights: on every shard that took part it equals the root's, bit
+ * for bit.
  *
  * eegfx_glm_count_sharded: counts = {tp, tn, fp, fn} in eegfx_confusion_counts' reading, of the
  * model's predictions (grad 0: LogisticRegressionModel, grad 1: SVMModel; threshold NaN: the raw

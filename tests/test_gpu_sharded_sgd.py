@@ -1,8 +1,9 @@
 """Data-parallel SGD over shards (csrc/sharded.cpp, logreg.hip's lr_fold_kernel and
 lr_count_kernel, eegfx_odp_split_sharded).
 
-One shard must give the bits of the one-context trainer (the shared fold order and the driver's
-plumbing against code that test_gpu_logreg_shapes.py pins); k shards are held to the long-double
+One shard must give the bits of the one-context entries, which run the same driver with their
+context as its one shard (two doors to the code that test_gpu_logreg_shapes.py pins, the second
+also with positions), and those entries leave a lone shard's state behind; k shards are held to the long-double
 restatement of tests/logreg_reference.py at that file's bars: weights within 1e-9 relative, the
 same iteration count, counts exact.  Context i lives on device i % eegfx_device_count(): a box that
 shows one GPU runs every case with its contexts sharing that device."""
@@ -109,6 +110,40 @@ def test_one_shard_equals_the_one_context_entry_bit_for_bit(ctxs, kind, n, d):
                                                  on(ctxs[2], np.zeros(0)))],
             100, 1.0, 0.01, initial_weights=start)
         assert again[1] == want[1] and np.array_equal(bits(again[0]), bits(want[0]))
+
+
+@pytest.mark.parametrize("kind", ["logistic", "hinge"])
+def test_a_one_context_run_leaves_the_state_of_a_lone_shard(ctxs, kind):
+    """The one-context entries run the driver with their context as its one shard:
+    eegfx_glm_shard_state reads what they leave, and rows staged from the host give the bits of
+    rows on the device."""
+    n, d = 300, 48
+    X, y = lr.rows(n, d, 1000 * d + n)
+    ctx = ctxs[0]
+    fn = clf.svm_sgd_train if kind == "hinge" else clf.sgd_train
+    w, it = fn(ctx, on(ctx, X), on(ctx, y), 100, 1.0, 0.01)
+    s_it, flag, updates, s_w = clf.shard_state(ctx, d)
+    assert (s_it, flag) == (it, 1) and it > 0 and updates >= 1
+    assert np.array_equal(bits(s_w), bits(w)) and np.any(w != 0.0)
+    if kind == "logistic":
+        clf.sgd_train(ctx, on(ctx, X[::-1]), on(ctx, y[::-1]), 3, 1.0, 0.01)   # another state
+        hw, hit = clf.sgd_train(ctx, X, y, 100, 1.0, 0.01)
+        assert hit == it and np.array_equal(bits(hw), bits(w))
+        s_it, flag, updates, s_w = clf.shard_state(ctx, d)
+        assert (s_it, flag) == (it, 1) and updates >= 1 and np.array_equal(bits(s_w), bits(w))
+
+
+def test_one_shard_with_positions_equals_the_one_context_entry_bit_for_bit(ctxs):
+    """The lone shard's path with a position list, which the one-context entry never takes."""
+    n, d = 300, 48
+    X, y = lr.rows(n, d, 1000 * d + n)
+    ctx = ctxs[0]
+    Xd, yd = on(ctx, X), on(ctx, y)
+    want = clf.sgd_train(ctx, Xd, yd, 100, 1.0, 0.01, mini_batch_fraction=0.5, num_partitions=4)
+    got = clf.sgd_train_sharded([(ctx, Xd, yd, on(ctx, np.arange(n, dtype=np.int64)))], 100, 1.0,
+                                0.01, mini_batch_fraction=0.5, num_partitions=4)
+    assert got[1] == want[1] > 0 and np.array_equal(bits(got[0]), bits(want[0]))
+    assert np.any(got[0] != 0.0)
 
 
 # ---- k shards against the long-double restatement -----------------------------------------------
@@ -234,6 +269,40 @@ def test_refusals_are_the_one_context_entry_s(ctxs):
     # and the contexts are as good as before
     c = sc.FULL_CASES[2]
     check_against_restatement(contiguous_shards(ctxs, *sc.rows(c), c.sizes), c)
+
+
+@pytest.mark.parametrize("grad", [0, 1])
+def test_a_one_context_run_on_a_bad_label_is_refused_and_leaves_the_context_good(ctxs, grad):
+    n, d = 300, 48
+    X, y = lr.rows(n, d, 1000 * d + n)
+    yb = y.copy()
+    yb[-1] = 0.5
+    ctx = ctxs[0]
+    Xd, yd, ybd = on(ctx, X), on(ctx, y), on(ctx, yb)
+    start = lr.initial_weights(d)
+    torch.cuda.synchronize()
+
+    def raw(labels, w, it):
+        head = (ctx.handle, _lib.ptr(Xd), _lib.ptr(labels), n, d, 100, 1.0, 0.01, 1.0, 0.001)
+        tail = (_lib.ptr(w), ctypes.byref(it), _lib.MEM_DEVICE)
+        rc = (fx.lib().eegfx_svm_sgd_train(*head, *tail) if grad else
+              fx.lib().eegfx_logreg_sgd_train_partitioned(*head, 4, *tail))
+        return rc, fx.lib().eegfx_last_error().decode()
+
+    w, it = start.copy(), ctypes.c_int32(-5)
+    assert raw(ybd, w, it) == (_lib.EEGFX_EINVAL,
+                               "Input validation failed: labels must be 0.0 or 1.0")
+    assert np.array_equal(bits(w), bits(start)) and it.value == -5      # untouched
+    # the context is as good as a fresh one
+    fn = clf.svm_sgd_train if grad else clf.sgd_train
+    got = fn(ctx, Xd, yd, 100, 1.0, 0.01, initial_weights=start)
+    fresh = fx.Context(ctx.device, numerics="exact")
+    try:
+        want = fn(fresh, Xd, yd, 100, 1.0, 0.01, initial_weights=start)
+    finally:
+        fresh.close()
+    assert got[1] == want[1] > 0 and np.array_equal(bits(got[0]), bits(want[0]))
+    assert not np.array_equal(bits(got[0]), bits(start))
 
 
 # ---- counts -------------------------------------------------------------------------------------
